@@ -14,10 +14,17 @@ environment; `python bench.py --gpus N` without WORLD_SIZE starts the N rank pro
 (before anything touches the GPU) and exits with their status.  Default = weak scaling (64
 candidates per GPU); `--strong` splits the one 64-candidate batch across the ranks.
 
-Other sections of the same JSON line: sim3 (config 3), mlpnp (config 4 per-GPU share), events
-(config 5), single-event latency, and the SURVEY §8(f) neighbours (PoseOptimization, SearchByBoW,
-SearchBySim3, KeyFrameDatabase).  Every RANSAC section carries a cpu_baseline (the oracle
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only that: set-up, W warm-up steps, the
+K timed steps, one JSON line (metric, value, ms_per_step, ...).  `--dump-outputs DIR` also writes what
+the last timed step computed (the result records and every hypothesis's pose and inlier count) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+With `--full` the same JSON line carries the rest: the headline's roofline (a second, instrumented
+pass of the K steps), sim3 (config 3), mlpnp (config 4 per-GPU share), events (config 5),
+single-event latency, the world-1 RCCL check and the SURVEY §8(f) neighbours (PoseOptimization,
+SearchByBoW, SearchBySim3, KeyFrameDatabase).  Every RANSAC section carries a cpu_baseline (the oracle
 restatement on the host's cores: 1 core and all cores, 3 warm-up batches then the median of >= 10).
+The --no-* options and --eig-rows-ab narrow or extend a --full run; they do nothing without it.
 """
 import argparse
 import json
@@ -100,6 +107,12 @@ def parse():
     for s in ("sim3", "mlpnp", "events", "latency", "poseopt", "bow", "sim3match", "sim3opt", "kfdb", "config1",
               "rccl-check"):
         p.add_argument(f"--no-{s}", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the instrumented second pass and roofline of "
+                        "config 2, the CPU baselines, the other sections (narrowed by the --no-* options) and the "
+                        "world-1 RCCL check; without it the run warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the result records and the hypotheses of the last timed config-2 step as DIR/<name>.npy")
     p.add_argument("--only-headline", action="store_true", help="config 2 only (PMC passes)")
     p.add_argument("--eig-rows-ab", action="store_true",
                    help="single-event A/B of the rows-form eigen stage (off-default variant, DESIGN.md §9)")
@@ -107,6 +120,8 @@ def parse():
                    help="nccl (= RCCL over xGMI, the product path) or gloo (host collectives: lets N ranks "
                         "share fewer GPUs to rehearse the launch and gather on a 1-GPU box)")
     a = p.parse_args()
+    if not a.full:  # a plain run: the headline's set-up, warm-up and timed steps only
+        a.only_headline = a.no_cpu = True
     if a.only_headline:
         for s in ("sim3", "mlpnp", "events", "latency", "poseopt", "bow", "sim3match", "sim3opt", "kfdb", "config1",
                   "rccl_check"):
@@ -319,6 +334,11 @@ def run_pnp(engine, ctx, scenes, cand_ids, args, dist, rank, world):
     ctx.synchronize()
     barrier(dist)
     dt = time.perf_counter() - t0
+    last = outs.copy()  # iterate_raw returns a view of the batch's reused record buffer
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, solvers)
+    if not args.full:
+        return dict(seconds=dt, hyps=hyps, problems=C * args.steps, last=last)
     # Timed region 2 (roofline): the same K steps with HIP events around the kernels on the
     # context stream (eigen stage, betas, scan); events add gaps, so this pass is not the metric.
     ctx.enable_timing(True)
@@ -337,7 +357,29 @@ def run_pnp(engine, ctx, scenes, cand_ids, args, dist, rank, world):
     ctx.enable_timing(False)
     return dict(seconds=dt, seconds_instrumented=dt_inst, hyps=hyps, problems=C * args.steps,
                 solve_ms=solve_ms / max(launches, 1), scan_ms=scan_ms / max(launches, 1),
-                eig_ms=eig_ms / max(launches, 1), launches=launches, last=outs)
+                eig_ms=eig_ms / max(launches, 1), launches=launches, last=last)
+
+
+def dump_outputs(path, rec, solvers):
+    """--dump-outputs: what the last timed step computed, float32, one row per candidate.  The result
+    records its caller received (rsc_pnp_iterate_many): ok, no_more, n_inliers, iterations [C] (counts
+    far below 2^24, exact in float32) and T [C, 16] (the record's own float32).  In exhaustive mode no
+    candidate succeeds and those records are all alike, so every hypothesis of the step's last launch
+    goes with them: hypothesis_inliers [C, H] and hypothesis_poses [C, H, 12] (rsc_pnp_last_hypotheses;
+    rows past a candidate's own count are zero).  ~1 MB at the default shapes; with more candidates
+    than 60 MB of hypotheses hold, the hypotheses of the first candidates that fit."""
+    os.makedirs(path, exist_ok=True)
+    out = {name: rec[name] for name in rec.dtype.names}
+    per_cand = 13 * 4 * max(1, int(rec["iterations"].max()))
+    hyp = [s.last_hypotheses(4096) for s in solvers[:max(1, 60_000_000 // per_cand)]]
+    H = max(len(cnt) for cnt, _ in hyp)
+    out["hypothesis_inliers"] = np.zeros((len(hyp), H), np.float32)
+    out["hypothesis_poses"] = np.zeros((len(hyp), H, 12), np.float32)
+    for c, (cnt, pos) in enumerate(hyp):
+        out["hypothesis_inliers"][c, :len(cnt)] = cnt
+        out["hypothesis_poses"][c, :len(cnt)] = pos
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, np.float32))
 
 
 def cpu_baseline_pnp(scenes, args, threads):
@@ -1509,8 +1551,9 @@ def main():
                    "hypotheses_per_candidate": args.iters, "params": "SetRansacParameters(0.99,10,300,4,0.5,5.991)",
                    "parallelism": par},
         "poses_per_s": round(problems_total / dt, 2),
-        "roofline": headline_roofline(args, r),
     }
+    if args.full:
+        out["roofline"] = headline_roofline(args, r)
     if with_cpu:
         cb = cpu_baseline_pnp(scenes, args, threads)
         cb["host"] = host_cpus(threads)

@@ -12,5 +12,5 @@ echo "pytest rc=$rc" >> $OUT/tests.txt
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 for v in $SOVARS; do echo "== $v" >> $OUT/sim3opt_probe.txt; RSC_LIBRSC=tools/bin/librsc_$v.so timeout -k 10 200 python tools/sim3opt_probe.py >> $OUT/sim3opt_probe.txt 2>&1; done
 for v in $POVARS; do echo "== $v" >> $OUT/poseopt_probe.txt; RSC_LIBRSC=tools/bin/librsc_$v.so timeout -k 10 200 python tools/poseopt_probe.py >> $OUT/poseopt_probe.txt 2>&1; done
-timeout -k 10 300 python bench.py --no-cpu --no-sim3 --no-mlpnp --no-events --no-latency --no-bow --no-sim3match --no-kfdb --no-config1 --no-rccl-check > $OUT/bench_lm.json 2> $OUT/bench_lm.err
+timeout -k 10 300 python bench.py --full --no-cpu --no-sim3 --no-mlpnp --no-events --no-latency --no-bow --no-sim3match --no-kfdb --no-config1 --no-rccl-check > $OUT/bench_lm.json 2> $OUT/bench_lm.err
 echo done > $OUT/done

@@ -31,13 +31,14 @@ if [ -n "$SMOKE" ]; then
   timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smoke.txt 2>&1
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 fi
+REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 if [ -n "$PROF" ]; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu > $OUT/prof_bench.json 2> $OUT/prof.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- python3 $REPO/bench.py --full --no-cpu > $OUT/prof_bench.json 2> $OUT/prof.err
 fi
-PMCARGS="--no-cpu --only-headline --steps 5 --warmup 1"
+PMCARGS="--full --no-cpu --only-headline --steps 5 --warmup 1"
 if [ -n "$PMC" ]; then
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py $PMCARGS > $OUT/pmc_fetch.log 2>&1
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o w --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py $PMCARGS > $OUT/pmc_write.log 2>&1
@@ -52,7 +53,7 @@ if [ -n "$VARIANTS" ]; then
   # off-default A/B variants: their parity tests, the single-event A/B of the rows-form
   # eigen stage, the chase-only sink variants, and the VGPR-row chase library on the headline
   cd $GRAFT_REPO_ROOT
-  timeout -k 10 300 python bench.py --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --eig-rows-ab > $OUT/bench_eig_rows_ab.json 2> $OUT/bench_eig_rows_ab.err
+  timeout -k 10 300 python bench.py --full --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --eig-rows-ab > $OUT/bench_eig_rows_ab.json 2> $OUT/bench_eig_rows_ab.err
   timeout -k 10 120 tools/bin/qr_bench > $OUT/qr_bench.txt 2>&1
   for v in a b a b; do
     if [ $v = a ]; then L=orb-slam2-optimized_amd/lib/librsc.so; else L=tools/bin/librsc_ldsrows.so; fi
@@ -82,7 +83,7 @@ fi
 if [ -n "$LAT" ]; then
   # single-event latency with the eigen-form A/B (pairs vs rows)
   cd $GRAFT_REPO_ROOT
-  timeout -k 10 300 python bench.py --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --eig-rows-ab > $OUT/bench_eig_rows_ab.json 2> $OUT/bench_eig_rows_ab.err
+  timeout -k 10 300 python bench.py --full --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --eig-rows-ab > $OUT/bench_eig_rows_ab.json 2> $OUT/bench_eig_rows_ab.err
 fi
 if [ -n "$SPINAB" ]; then
   # host wait for a round: hipStreamSynchronize (0) vs spin on a pinned completion flag (1)
@@ -90,7 +91,7 @@ if [ -n "$SPINAB" ]; then
   for v in 0 1 0 1; do
     RSC_SPIN_WAIT=$v timeout -k 10 200 python bench.py --only-headline --no-cpu >> $OUT/spin_ab_$v.jsonl 2>> $OUT/spin_ab.err
     RSC_SPIN_WAIT=$v TIMING=0 timeout -k 10 120 python tools/host_overhead.py >> $OUT/host_overhead_spin$v.txt 2>&1
-    RSC_SPIN_WAIT=$v timeout -k 10 300 python bench.py --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-mlpnp --no-events --no-sim3 >> $OUT/spin_ab_lat_$v.jsonl 2>> $OUT/spin_ab.err
+    RSC_SPIN_WAIT=$v timeout -k 10 300 python bench.py --full --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-mlpnp --no-events --no-sim3 >> $OUT/spin_ab_lat_$v.jsonl 2>> $OUT/spin_ab.err
   done
 fi
 if [ -n "$PROBE" ]; then
@@ -100,8 +101,8 @@ if [ -n "$PROBE" ]; then
 fi
 if [ -n "$GPUS2" ]; then
   cd $GRAFT_REPO_ROOT
-  timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --no-cpu --no-latency --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --steps 8 --warmup 2 > $OUT/bench_gpus2_gloo.json 2> $OUT/bench_gpus2_gloo.err
-  timeout -k 10 300 python bench.py --gpus 4 --dist-backend gloo --no-cpu --no-latency --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --steps 8 --warmup 2 > $OUT/bench_gpus4_gloo.json 2> $OUT/bench_gpus4_gloo.err
+  timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --no-cpu --no-latency --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --steps 8 --warmup 2 > $OUT/bench_gpus2_gloo.json 2> $OUT/bench_gpus2_gloo.err
+  timeout -k 10 300 python bench.py --full --gpus 4 --dist-backend gloo --no-cpu --no-latency --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --steps 8 --warmup 2 > $OUT/bench_gpus4_gloo.json 2> $OUT/bench_gpus4_gloo.err
 fi
 if [ -n "$REFAB" ]; then
   # Refine phase stamps of the single relocalization event for stamped builds of the libraries named
@@ -120,7 +121,7 @@ if [ -n "$LIBAB" ]; then
   for rep in 1 2; do
     for v in $LIBAB; do
       if [ $v = product ]; then L=orb-slam2-optimized_amd/lib/librsc.so; else L=tools/bin/librsc_$v.so; fi
-      step env RSC_LIBRSC=$L timeout -k 10 300 python bench.py --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-mlpnp --no-events --no-sim3 >> $OUT/libab_$v.jsonl 2>> $OUT/libab.err
+      step env RSC_LIBRSC=$L timeout -k 10 300 python bench.py --full --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-mlpnp --no-events --no-sim3 >> $OUT/libab_$v.jsonl 2>> $OUT/libab.err
     done
   done
 fi
@@ -171,7 +172,7 @@ if [ -n "$ENVAB" ]; then
   cd $GRAFT_REPO_ROOT
   for rep in 1 2; do
     for v in $ENVAB; do
-      step env $v timeout -k 10 300 python bench.py --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-mlpnp --no-events --no-sim3 >> $OUT/envab_$v.jsonl 2>> $OUT/envab.err
+      step env $v timeout -k 10 300 python bench.py --full --no-cpu --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-mlpnp --no-events --no-sim3 >> $OUT/envab_$v.jsonl 2>> $OUT/envab.err
     done
   done
 fi

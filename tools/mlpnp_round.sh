@@ -6,7 +6,7 @@ TAG=${TAG:-ml}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-ONLY="--no-cpu --no-sim3 --no-events --no-latency --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-rccl-check"
+ONLY="--full --no-cpu --no-sim3 --no-events --no-latency --no-poseopt --no-bow --no-sim3match --no-sim3opt --no-kfdb --no-config1 --no-rccl-check"
 if [ -z "$NO_TESTS" ]; then
   timeout -k 10 600 python -u -m pytest tests/test_gpu_mlpnp.py tests/test_gpu_configs.py -x -v --timeout 300 --timeout-method thread > $OUT/tests.txt 2>&1
 fi

@@ -13,6 +13,6 @@ for v in a b a b a b; do
 done
 for v in a b; do
   if [ $v = a ]; then L=orb-slam2-optimized_amd/lib/librsc.so; else L=${LIBB:-tools/bin/librsc_nancheck1.so}; fi
-  RSC_LIBRSC=$L timeout -k 10 300 python bench.py --no-cpu > $OUT/full_$v.json 2>> $OUT/ab.err
+  RSC_LIBRSC=$L timeout -k 10 300 python bench.py --full --no-cpu > $OUT/full_$v.json 2>> $OUT/ab.err
 done
 echo done > $OUT/done
