@@ -1,5 +1,5 @@
 # Build of the MI355X RANSAC pose engine (gfx950).  `make` builds librsc.so (HIP kernels + C ABI),
-# the oracle (test infrastructure) and the host-emulation test library.
+# the oracle (test infrastructure) and the host-emulation test libraries.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 PKG = orb-slam2-optimized_amd
@@ -9,7 +9,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fa
            -fno-gpu-flush-denormals-to-zero -Wall -Wno-unused-function -Wno-unused-variable
 HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
-all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu facade_test
+all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu facade_test facade_proj_test
 
 $(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
@@ -35,6 +35,10 @@ $(LIBDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/frameproj.o: $(CSRC)/frameproj.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/kfdb.o: $(CSRC)/kfdb.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -43,7 +47,7 @@ $(LIBDIR)/rsc_api.o: $(CSRC)/rsc_api.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/kfdb.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 # TEST-ONLY variant: the split eigen stage's hand-off waits give up after one poll, so the fault path
@@ -52,7 +56,7 @@ $(LIBDIR)/kernels_spin1.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DRSC_SPLIT_SPIN_LIMIT=1 -c $< -o $@
 
-$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/kfdb.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 facade_test: $(LIBDIR)/facade_test
@@ -60,13 +64,21 @@ facade_test: $(LIBDIR)/facade_test
 $(LIBDIR)/facade_test: tests/cpp/facade_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
 	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
 
+facade_proj_test: $(LIBDIR)/facade_proj_test
+
+$(LIBDIR)/facade_proj_test: tests/cpp/facade_proj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
+	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_proj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+
 oracle:
 	$(MAKE) -s -C oracle
 
 hostemu:
 	$(MAKE) -s -C tests/hostemu
 
-clean:
-	rm -rf $(LIBDIR) oracle/build tests/hostemu/build
+frameproj_emu:
+	$(MAKE) -s -C tests/frameproj_emu
 
-.PHONY: all oracle hostemu facade_test clean
+clean:
+	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build
+
+.PHONY: all oracle hostemu frameproj_emu facade_test facade_proj_test clean

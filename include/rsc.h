@@ -286,10 +286,10 @@ int rsc_loop_events_shared(rsc_sim3* const* solvers, const int32_t* event_begin,
  * iterate() record. */
 #define RSC_GATE_NONE 0    /* every candidate discarded without an accepted pose (bMatch false) */
 #define RSC_GATE_MATCH 1   /* a success passed the gate (bMatch = true) */
-#define RSC_GATE_HANDOFF 2 /* relocalization: 10 <= nGood < 50 after PoseOptimization; the reference runs
-                              SearchByProjection next (Tracking.cpp:1294-1323, outside this engine) —
-                              the event stops here and the host continues it (the records of the
-                              candidates after the winner in its round are already those calls' results) */
+#define RSC_GATE_HANDOFF 2 /* rsc_reloc_events_gated only: 10 <= nGood < 50 after PoseOptimization, where the
+                              reference runs its SearchByProjection refinement (Tracking.cpp:1294-1323).  This
+                              driver stops the event there; rsc_reloc_events_refined (below) runs that chain on
+                              the device and carries the round-robin on, so it never returns this status */
 /* Tracking::Relocalization (Tracking.cpp:1239-1335).  The current Frame's data PoseOptimization reads
  * beyond what the solvers hold (their compacted p2d / p3dw / sigma2 are Frame::mvKeysUn, the MapPoint
  * positions and mvLevelSigma2; mvInvLevelSigma2 = 1.0f / mvLevelSigma2 as ORBextractor sets it). */
@@ -492,6 +492,102 @@ void rsc_kfview_destroy(rsc_kfview* view);
 int rsc_search_by_sim3_many(rsc_context* ctx, rsc_kfview* const* kf1, rsc_kfview* const* kf2, int count,
                             const float* R12, const float* t12, float th, const int32_t* const* matched12,
                             int32_t* const* out12, int32_t* nfound);
+
+/* ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame, sAlreadyFound, th, ORBdist) ------------------
+ * (src/ORBmatcher.cpp:1317-1444 with Frame::GetFeaturesInArea, src/Frame.cpp:394-447): the matcher of
+ * Tracking::Relocalization's refinement (Tracking.cpp:1296, :1310).  Every MapPoint of the candidate
+ * KeyFrame that is not in sAlreadyFound is projected with the Frame's pose and takes the free Frame
+ * feature of the predicted levels [L-1, L+1] with the smallest descriptor distance (<= ORBdist) inside
+ * th * scale[L] of the projection; features claimed by earlier MapPoints of the same call are not
+ * free (the reference's sequential order is reproduced exactly), then the rotation histogram removes
+ * the matches outside its three best bins.  Quirks kept: no z > 0 test, inclusive image bounds.
+ * Precondition: no eligible MapPoint has camera-frame z == 0 (undefined in the reference). */
+typedef struct {
+    int32_t n;                  /* Frame::N, <= 8192 */
+    const float* kp;            /* [n][2] mvKeysUn[i].pt */
+    const int32_t* octave;      /* [n] mvKeysUn[i].octave */
+    const float* angle;         /* [n] mvKeysUn[i].angle */
+    const uint8_t* desc;        /* [n][32] mDescriptors */
+    const int32_t* cell_begin;  /* [64*48 + 1] CSR over mGrid[ix][iy] (cell = ix * 48 + iy) */
+    const int32_t* cell_feat;   /* mGrid contents, each cell's vector<size_t> in order */
+    float min_x, max_x, min_y, max_y;  /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    float grid_w_inv, grid_h_inv;      /* mfGridElementWidthInv, mfGridElementHeightInv */
+    float fx, fy, cx, cy;
+    const float* scale_factors; /* [n_levels] mvScaleFactors */
+    int32_t n_levels;           /* mnScaleLevels, <= 64 */
+    float log_scale_factor;     /* mfLogScaleFactor */
+} rsc_frame_features;
+
+typedef struct rsc_frameview rsc_frameview;
+/* Upload the current Frame as the matcher reads it to HBM (host copies of the keypoints, octaves and
+ * 1 / sigma^2 per level are kept for the PoseOptimization problems of rsc_reloc_refine_many). */
+int rsc_frameview_create(rsc_context* ctx, const rsc_frame_features* frame, rsc_frameview** out);
+void rsc_frameview_destroy(rsc_frameview* view);
+/* The KeyFrame's keypoint angles, angle[i] = mvKeysUn[i].angle (view n entries): the rotation check of
+ * SearchByProjection reads them and rsc_sim3_kf carries none. */
+int rsc_kfview_set_angles(rsc_kfview* view, const float* angle);
+
+/* SearchByProjection(CurrentFrame = frames[c], pKF = kfs[c], sAlreadyFound, th, ORBdist) for c < count in
+ * one launch (one workgroup per problem).  Tcw [count][16]: CurrentFrame.mTcw, row-major.
+ * already[c][i] (kfs[c] n entries): sAlreadyFound.count(vpMPs[i]).  frame_mp[c][f] (frames[c] n
+ * entries) >= 0: CurrentFrame.mvpMapPoints[f] is set before the call (not modified).  out[c][f]: the
+ * KeyFrame slot whose MapPoint the call writes to mvpMapPoints[f] and the rotation check keeps, else
+ * -1; nmatches[c] = the return value; rounds (may be NULL): fixed-point rounds run (diagnostic).
+ * check_orientation = mbCheckOrientation: needs rsc_kfview_set_angles on every kfs[c] (RSC_ERR_ARG
+ * otherwise).  orb_dist outside [0, 255] is RSC_ERR_ARG. */
+int rsc_search_by_projection_many(rsc_context* ctx, rsc_frameview* const* frames, rsc_kfview* const* kfs, int count,
+                                  const float* Tcw, const uint8_t* const* already, const int32_t* const* frame_mp,
+                                  float th, int orb_dist, int check_orientation, int32_t* const* out,
+                                  int32_t* nmatches, int32_t* rounds);
+
+/* Tracking::Relocalization's refinement chain (Tracking.cpp:1294-1323) for `count` candidates:
+ * SearchByProjection(10, 100) -> PoseOptimization when nadditional + nGood >= 50 -> for 30 < nGood < 50
+ * SearchByProjection(3, 64) with sFound = every occupied slot -> PoseOptimization and removal of its
+ * outliers when nGood + nadditional >= 50.  Each stage is one launch over the candidates still in the
+ * chain; each search reads the pose the optimisation before it wrote. */
+typedef struct {
+    int32_t n_good;           /* nGood after the chain (n_good_in when no optimisation ran) */
+    int32_t n_additional[2];  /* SearchByProjection's return values, -1 when the stage did not run */
+    int32_t pose_opts;        /* PoseOptimization runs, 0..2 */
+    float Tcw[16];            /* mCurrentFrame.mTcw after the chain */
+} rsc_reloc_refine_result;
+/* frame_mp[c][f] (in/out, frames[c] n entries): the KeyFrame slot of mCurrentFrame.mvpMapPoints[f] or
+ * -1, on entry after the outliers of the first PoseOptimization were removed (:1289-1291).  found[c]
+ * (kfs[c] n entries): sFound as built at :1278, from ALL RANSAC inliers.  n_good_in / Tcw_in
+ * [count][16]: nGood and mTcw of that first PoseOptimization.  fr[c]: the Frame's mvuRight / mbf.  The
+ * optimisations read uv = the Frame keypoint, Xw = the KeyFrame view's mp_pos[slot], inv_sigma2 =
+ * 1.0f / (s * s) with s = the scale factor of the Frame keypoint's octave. */
+int rsc_reloc_refine_many(rsc_context* ctx, rsc_frameview* const* frames, rsc_kfview* const* kfs, int count,
+                          const rsc_reloc_frame* fr, int32_t* const* frame_mp, const uint8_t* const* found,
+                          const int32_t* n_good_in, const float* Tcw_in, rsc_reloc_refine_result* out);
+
+/* Tracking::Relocalization (Tracking.cpp:1239-1335) from the candidate solvers to bMatch: the loop of
+ * rsc_reloc_events_gated with the refinement chain inside.  A success with 10 <= nGood < 50 goes
+ * through rsc_reloc_refine_many (batched over the events of the pass); nGood >= 50 afterwards is
+ * RSC_GATE_MATCH, otherwise the walk continues with the next success of the round (:1327-1333).
+ * status is RSC_GATE_MATCH or RSC_GATE_NONE.  Own-stream solvers only (RSC_ERR_UNSUPPORTED). */
+typedef struct {
+    rsc_kfview* kf;          /* vpCandidateKFs[i] (with angles) */
+    const int32_t* matches;  /* [Frame n] vvpMapPointMatches[i] as KeyFrame slots, -1 NULL: the output of
+                                rsc_search_by_bow_frame_many the candidate's solver was built from */
+} rsc_reloc_candidate;
+typedef struct {
+    int32_t status, winner, round, hypothesis, n_inliers;  /* as rsc_reloc_gate_result */
+    int32_t n_good;           /* nGood of the accepted success at :1327 (after its chain, if one ran) */
+    int32_t rejected;         /* successes rejected before it (nGood < 10, or < 50 after the chain) */
+    int32_t gates;            /* first PoseOptimization runs of the event */
+    int32_t n_good_first;     /* the winner's nGood at :1284 */
+    int32_t n_additional[2];  /* the winner's chain (-1: stage not run) */
+    int32_t chains;           /* refinement chains run in the event */
+    float Tcw[16];            /* mCurrentFrame.mTcw of the accepted success */
+} rsc_reloc_refined_result;
+/* views[e]: event e's current Frame; candidates[i]: per solver.  frame_mp_out[e] (may be NULL / NULL
+ * entries): [Frame n] mCurrentFrame.mvpMapPoints of the accepted success as KeyFrame slots of the
+ * winner (-1 NULL); untouched for RSC_GATE_NONE. */
+int rsc_reloc_events_refined(rsc_pnp* const* solvers, const rsc_reloc_candidate* candidates,
+                             const int32_t* event_begin, int n_events, rsc_frameview* const* views,
+                             const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
+                             rsc_reloc_refined_result* per_event, int32_t* const* frame_mp_out);
 
 /* ---- KeyFrameDatabase: BoW candidate scoring (src/KeyFrameDatabase.cpp) ---------------------- */
 /* A device-resident keyframe database: each KeyFrame is a slot in [0, capacity) holding its

@@ -23,9 +23,16 @@
 // image bounds, Frame assigned it with float bounds) and MapPoint::GetMaxDistance()/GetMinDistance()
 // (mfMaxDistance/mfMinDistance: GetMaxDistanceInvariance() returns 1.2f*mfMaxDistance, which does
 // not round-trip in float).
+//
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1317-1444; the
+// refinement of Tracking::Relocalization, Tracking.cpp:1296 and :1310) reads the KeyFrame as SearchBySim3
+// does plus mvKeysUn[i].angle, and of the Frame only public members (include/Frame.hpp): N, mvKeysUn,
+// mDescriptors, mGrid, mnMinX..mnMaxY, mfGridElementWidthInv/HeightInv, fx..cy, mvScaleFactors,
+// mnScaleLevels, mfLogScaleFactor, mTcw (rotation() / translation()) and mvpMapPoints, which it writes.
 #pragma once
 #include <algorithm>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <vector>
 #include "rsc_context.hpp"
@@ -178,6 +185,59 @@ KFViewUpload upload_kfview(const KFPtr& pKF, const std::vector<MPPtr>& mps) {
     KFViewUpload u;
     u.n = n;
     check(rsc_kfview_create(thread_context(), &k, &u.h), "rsc_kfview_create");
+    return u;
+}
+
+// The current Frame's SearchByProjection inputs uploaded to HBM (rsc_frameview_create).
+struct FrameViewUpload {
+    rsc_frameview* h = nullptr;
+    int n = 0;
+    FrameViewUpload() = default;
+    FrameViewUpload(const FrameViewUpload&) = delete;
+    FrameViewUpload& operator=(const FrameViewUpload&) = delete;
+    FrameViewUpload(FrameViewUpload&& o) noexcept : h(o.h), n(o.n) { o.h = nullptr; }
+    ~FrameViewUpload() { rsc_frameview_destroy(h); }
+};
+
+template <class FrameT>
+FrameViewUpload upload_frameview(const FrameT& F) {
+    const int n = (int)F.N;
+    std::vector<float> kp(2 * (size_t)n), ang((size_t)n);
+    std::vector<int32_t> oct((size_t)n);
+    std::vector<uint8_t> desc(32 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        kp[2 * i] = F.mvKeysUn[i].pt.x;
+        kp[2 * i + 1] = F.mvKeysUn[i].pt.y;
+        oct[i] = F.mvKeysUn[i].octave;
+        ang[i] = F.mvKeysUn[i].angle;
+        const uint8_t* row = F.mDescriptors.template ptr<uint8_t>(i);
+        std::copy(row, row + 32, desc.begin() + 32 * (size_t)i);
+    }
+    std::vector<int32_t> begin(1, 0), feat;  // mGrid[ix][iy] -> CSR over cell = ix * 48 + iy
+    for (int ix = 0; ix < 64; ++ix)
+        for (int iy = 0; iy < 48; ++iy) {
+            for (auto f : F.mGrid[ix][iy]) feat.push_back((int32_t)f);
+            begin.push_back((int32_t)feat.size());
+        }
+    if (feat.empty()) feat.push_back(0);
+    rsc_frame_features f;
+    f.n = n;
+    f.kp = kp.data();
+    f.octave = oct.data();
+    f.angle = ang.data();
+    f.desc = desc.data();
+    f.cell_begin = begin.data();
+    f.cell_feat = feat.data();
+    f.min_x = F.mnMinX; f.max_x = F.mnMaxX; f.min_y = F.mnMinY; f.max_y = F.mnMaxY;
+    f.grid_w_inv = F.mfGridElementWidthInv;
+    f.grid_h_inv = F.mfGridElementHeightInv;
+    f.fx = F.fx; f.fy = F.fy; f.cx = F.cx; f.cy = F.cy;
+    f.scale_factors = F.mvScaleFactors.data();
+    f.n_levels = (int32_t)F.mnScaleLevels;
+    f.log_scale_factor = F.mfLogScaleFactor;
+    FrameViewUpload u;
+    u.n = n;
+    check(rsc_frameview_create(thread_context(), &f, &u.h), "rsc_frameview_create");
     return u;
 }
 
@@ -337,6 +397,101 @@ public:
                 if (out[c][i] >= 0) m[i] = mp2[out[c][i]];
         }
         return std::vector<int>(nfound.begin(), nfound.begin() + C);
+    }
+
+    // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1317-1444): the
+    // MapPoints of pKF that are not in sAlreadyFound are projected with CurrentFrame.mTcw and matched to
+    // the free features of the Frame; the new matches are written to CurrentFrame.mvpMapPoints (those the
+    // rotation check removes are not), returns their number.
+    template <class FrameT, class KFPtr, class MPPtr>
+    int SearchByProjection(FrameT& CurrentFrame, KFPtr pKF, const std::set<MPPtr>& sAlreadyFound, const float th,
+                           const int ORBdist) {
+        std::vector<FrameT*> f(1, &CurrentFrame);
+        std::vector<KFPtr> k(1, pKF);
+        std::vector<const std::set<MPPtr>*> s(1, &sAlreadyFound);
+        return SearchByProjectionMany(f, k, s, th, ORBdist)[0];
+    }
+
+    // SearchByProjection(*frames[c], vpKFs[c], *sAlreadyFound[c], th, ORBdist) for several candidates in
+    // one launch.  Each Frame and KeyFrame object is uploaded once; problems that share a Frame object all
+    // read its mvpMapPoints as they were at the call (give each candidate its own Frame copy, as a
+    // relocalization that evaluates candidates side by side does).
+    template <class FrameT, class KFPtr, class MPPtr>
+    std::vector<int> SearchByProjectionMany(const std::vector<FrameT*>& frames, const std::vector<KFPtr>& vpKFs,
+                                            const std::vector<const std::set<MPPtr>*>& sAlreadyFound, const float th,
+                                            const int ORBdist) {
+        const int C = (int)frames.size();
+        std::vector<const void*> fkeys, kkeys;
+        std::vector<detail::FrameViewUpload> fviews;
+        std::vector<detail::KFViewUpload> kviews;
+        std::vector<std::vector<MPPtr>> mps;
+        std::vector<int> fi(C), ki(C);
+        for (int c = 0; c < C; ++c) {
+            size_t j = 0;
+            for (; j < fkeys.size(); ++j)
+                if (fkeys[j] == (const void*)frames[c]) break;
+            if (j == fkeys.size()) {
+                fkeys.push_back((const void*)frames[c]);
+                fviews.push_back(detail::upload_frameview(*frames[c]));
+            }
+            fi[c] = (int)j;
+            for (j = 0; j < kkeys.size(); ++j)
+                if (kkeys[j] == (const void*)&*vpKFs[c]) break;
+            if (j == kkeys.size()) {
+                kkeys.push_back((const void*)&*vpKFs[c]);
+                mps.push_back(vpKFs[c]->GetMapPointMatches());
+                kviews.push_back(detail::upload_kfview(vpKFs[c], mps.back()));
+                const int n = kviews.back().n;
+                std::vector<float> ang((size_t)(n > 0 ? n : 1), 0.f);
+                for (int i = 0; i < n; ++i) ang[i] = vpKFs[c]->mvKeysUn[i].angle;
+                check(rsc_kfview_set_angles(kviews.back().h, ang.data()), "rsc_kfview_set_angles");
+            }
+            ki[c] = (int)j;
+        }
+        std::vector<rsc_frameview*> hf(C);
+        std::vector<rsc_kfview*> hk(C);
+        std::vector<float> T(16 * (size_t)(C > 0 ? C : 1), 0.f);
+        std::vector<std::vector<uint8_t>> already(C);
+        std::vector<std::vector<int32_t>> occ(C), out(C);
+        std::vector<const uint8_t*> pal(C);
+        std::vector<const int32_t*> pocc(C);
+        std::vector<int32_t*> pout(C);
+        for (int c = 0; c < C; ++c) {
+            FrameT& F = *frames[c];
+            hf[c] = fviews[fi[c]].h;
+            hk[c] = kviews[ki[c]].h;
+            const auto R = F.mTcw.rotation();
+            const auto t = F.mTcw.translation();
+            for (int r = 0; r < 3; ++r) {
+                for (int k = 0; k < 3; ++k) T[16 * (size_t)c + 4 * r + k] = R(r, k);
+                T[16 * (size_t)c + 4 * r + 3] = t(r);
+            }
+            T[16 * (size_t)c + 15] = 1.f;
+            const std::vector<MPPtr>& m = mps[ki[c]];
+            const int nk = kviews[ki[c]].n, nf = fviews[fi[c]].n;
+            already[c].assign((size_t)(nk > 0 ? nk : 1), 0);
+            for (int i = 0; i < nk && (size_t)i < m.size(); ++i)
+                if (m[i] && sAlreadyFound[c]->count(m[i])) already[c][i] = 1;
+            occ[c].assign((size_t)(nf > 0 ? nf : 1), -1);
+            out[c].assign((size_t)(nf > 0 ? nf : 1), -1);
+            for (int i = 0; i < nf && (size_t)i < F.mvpMapPoints.size(); ++i)
+                if (F.mvpMapPoints[i]) occ[c][i] = 0;
+            pal[c] = already[c].data();
+            pocc[c] = occ[c].data();
+            pout[c] = out[c].data();
+        }
+        std::vector<int32_t> nm(C > 0 ? C : 1, 0);
+        check(rsc_search_by_projection_many(thread_context(), hf.data(), hk.data(), C, T.data(), pal.data(),
+                                            pocc.data(), th, ORBdist, mbCheckOrientation ? 1 : 0, pout.data(),
+                                            nm.data(), nullptr),
+              "SearchByProjection(Frame, KeyFrame)");
+        for (int c = 0; c < C; ++c) {  // CurrentFrame.mvpMapPoints[bestIdx2] = pMP (:1402)
+            FrameT& F = *frames[c];
+            const std::vector<MPPtr>& m = mps[ki[c]];
+            for (int i = 0; i < fviews[fi[c]].n && (size_t)i < F.mvpMapPoints.size(); ++i)
+                if (out[c][i] >= 0) F.mvpMapPoints[i] = m[out[c][i]];
+        }
+        return std::vector<int>(nm.begin(), nm.begin() + C);
     }
 
 private:

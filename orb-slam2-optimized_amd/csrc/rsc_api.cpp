@@ -24,6 +24,7 @@
 #include "rsc_sim3opt.h"
 #include "rsc_orbmatch.h"
 #include "rsc_sim3match.h"
+#include "rsc_frameproj.h"
 #include "rsc_kfdb.h"
 
 using namespace rsc;
@@ -205,6 +206,9 @@ struct rsc_context {
     // SearchByBoW: pair table + output vectors + match counts (device, pinned mirror)
     DevBuf<char> d_bow;
     PinBuf<char> h_bow;
+    // SearchByProjection (Frame, KeyFrame): problem table + flags + per-MapPoint scratch + outputs
+    DevBuf<char> d_fp;
+    PinBuf<char> h_fp;
     int mask_words = 0;  // per hypothesis, last speculation
     bool keep_samples = true;
     // timing
@@ -2181,6 +2185,9 @@ struct rsc_kfview {
     std::vector<int32_t> octave;
     std::vector<uint8_t> mp_state;
     float R[9], t[3], K[4];
+    DevSim3KF dev;           // the header as uploaded (device pointers), for SearchByProjection's problem table
+    DevBuf<float> d_angle;   // mvKeysUn[i].angle (rsc_kfview_set_angles)
+    bool has_angles = false;
 };
 
 int rsc_kfview_create(rsc_context* C, const rsc_sim3_kf* k, rsc_kfview** out) {
@@ -2226,6 +2233,7 @@ int rsc_kfview_create(rsc_context* C, const rsc_sim3_kf* k, rsc_kfview** out) {
     std::memcpy(b.h.data() + o_hdr, &h, sizeof(h));
     RSC_HIP(hipMemcpy(d, b.h.data(), b.h.size(), hipMemcpyHostToDevice));
     v->hdr = reinterpret_cast<const DevSim3KF*>(d + o_hdr);
+    v->dev = h;
     v->kp.assign(k->kp, k->kp + 2 * n);
     v->octave.assign(k->octave, k->octave + n);
     v->mp_state.assign(k->mp_state, k->mp_state + n);
@@ -2329,6 +2337,325 @@ int rsc_search_by_sim3_many(rsc_context* C, rsc_kfview* const* kf1, rsc_kfview* 
         if (nfound) std::memcpy(&nfound[c], h + o_nf[c], 4);
     }
     return RSC_OK;
+}
+
+// ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame, sAlreadyFound, th, ORBdist) (rsc_frameproj.h) ----
+struct rsc_frameview {
+    rsc_context* ctx = nullptr;
+    int n = 0;
+    DevBuf<char> mem;  // DevProjFrame header | kp | octave | angle | desc | grid | scales
+    const DevProjFrame* hdr = nullptr;
+    // host copies of what the refinement chain's PoseOptimization problems read
+    std::vector<float> kp, inv_level_sigma2;
+    std::vector<int32_t> octave;
+    float K[4];
+};
+
+int rsc_frameview_create(rsc_context* C, const rsc_frame_features* f, rsc_frameview** out) {
+    if (!C || !f || !out) return RSC_ERR_ARG;
+    *out = nullptr;
+    if (f->n < 0 || f->n > kProjMaxFeatures || f->n_levels < 1 || f->n_levels > 64 || !f->cell_begin ||
+        !f->scale_factors)
+        return RSC_ERR_ARG;
+    if (f->n > 0 && (!f->kp || !f->octave || !f->angle || !f->desc)) return RSC_ERR_ARG;
+    const int cells = kProjGridCols * kProjGridRows;
+    if (f->cell_begin[0] != 0) return RSC_ERR_ARG;
+    for (int c = 0; c < cells; ++c)
+        if (f->cell_begin[c + 1] < f->cell_begin[c]) return RSC_ERR_ARG;
+    const size_t n = (size_t)f->n, nf = (size_t)f->cell_begin[cells];
+    if (nf > 0 && !f->cell_feat) return RSC_ERR_ARG;
+    for (size_t e = 0; e < nf; ++e)
+        if (f->cell_feat[e] < 0 || f->cell_feat[e] >= f->n) {
+            g_last_error = "mGrid index out of range";
+            return RSC_ERR_ARG;
+        }
+    for (size_t i = 0; i < n; ++i)
+        if (f->octave[i] < 0 || f->octave[i] >= f->n_levels) {
+            g_last_error = "keypoint octave out of range";
+            return RSC_ERR_ARG;
+        }
+    S3Blob b;
+    const size_t o_hdr = b.reserve(sizeof(DevProjFrame));
+    const size_t o_kp = b.add(f->kp, 8 * n), o_oct = b.add(f->octave, 4 * n), o_ang = b.add(f->angle, 4 * n);
+    const size_t o_desc = b.add(f->desc, 32 * n), o_cb = b.add(f->cell_begin, 4 * (size_t)(cells + 1));
+    const size_t o_cf = b.add(f->cell_feat, 4 * nf), o_sc = b.add(f->scale_factors, 4 * (size_t)f->n_levels);
+    std::unique_ptr<rsc_frameview> v(new rsc_frameview);
+    v->ctx = C;
+    v->n = f->n;
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = v->mem.ensure(b.h.size())) return e;
+    char* d = v->mem.p;
+    DevProjFrame h;
+    h.kp = reinterpret_cast<const ProjPt*>(d + o_kp);
+    h.octave = reinterpret_cast<const int32_t*>(d + o_oct);
+    h.angle = reinterpret_cast<const float*>(d + o_ang);
+    h.desc = reinterpret_cast<const ProjDesc*>(d + o_desc);
+    h.cell_begin = reinterpret_cast<const int32_t*>(d + o_cb);
+    h.cell_feat = reinterpret_cast<const int32_t*>(d + o_cf);
+    h.scale = reinterpret_cast<const float*>(d + o_sc);
+    h.min_x = f->min_x; h.max_x = f->max_x; h.min_y = f->min_y; h.max_y = f->max_y;
+    h.gw_inv = f->grid_w_inv; h.gh_inv = f->grid_h_inv;
+    h.fx = f->fx; h.fy = f->fy; h.cx = f->cx; h.cy = f->cy;
+    h.log_sf = f->log_scale_factor;
+    h.n = f->n;
+    h.n_levels = f->n_levels;
+    std::memcpy(b.h.data() + o_hdr, &h, sizeof(h));
+    RSC_HIP(hipMemcpy(d, b.h.data(), b.h.size(), hipMemcpyHostToDevice));
+    v->hdr = reinterpret_cast<const DevProjFrame*>(d + o_hdr);
+    v->kp.assign(f->kp, f->kp + 2 * n);
+    v->octave.assign(f->octave, f->octave + n);
+    v->inv_level_sigma2.resize((size_t)f->n_levels);
+    for (int l = 0; l < f->n_levels; ++l) {  // mvInvLevelSigma2 as ORBextractor sets it (see rsc_kfview_create)
+        const float s2 = f->scale_factors[l] * f->scale_factors[l];
+        v->inv_level_sigma2[l] = 1.0f / s2;
+    }
+    v->K[0] = f->fx; v->K[1] = f->fy; v->K[2] = f->cx; v->K[3] = f->cy;
+    *out = v.release();
+    return RSC_OK;
+}
+
+void rsc_frameview_destroy(rsc_frameview* v) {
+    if (!v) return;
+    (void)hipStreamSynchronize(v->ctx->stream);
+    delete v;
+}
+
+int rsc_kfview_set_angles(rsc_kfview* v, const float* angle) {
+    if (!v || (v->n > 0 && !angle)) return RSC_ERR_ARG;
+    RSC_HIP(hipSetDevice(v->ctx->device));
+    if (int e = v->d_angle.ensure((size_t)std::max(v->n, 1))) return e;
+    RSC_HIP(hipStreamSynchronize(v->ctx->stream));
+    if (v->n) RSC_HIP(hipMemcpy(v->d_angle.p, angle, 4 * (size_t)v->n, hipMemcpyHostToDevice));
+    v->has_angles = true;
+    return RSC_OK;
+}
+
+int rsc_search_by_projection_many(rsc_context* C, rsc_frameview* const* frames, rsc_kfview* const* kfs, int count,
+                                  const float* Tcw, const uint8_t* const* already, const int32_t* const* frame_mp,
+                                  float th, int orb_dist, int check_orientation, int32_t* const* out,
+                                  int32_t* nmatches, int32_t* rounds) {
+    if (!C || count < 0) return RSC_ERR_ARG;
+    if (orb_dist < 0 || orb_dist > 255) {  // the reference would write mvpMapPoints[-1] (bestDist starts at 256)
+        g_last_error = "ORBdist outside [0, 255]";
+        return RSC_ERR_ARG;
+    }
+    if (count == 0) return RSC_OK;
+    if (!frames || !kfs || !Tcw || !already || !frame_mp || !out) return RSC_ERR_ARG;
+    for (int c = 0; c < count; ++c) {
+        if (!frames[c] || !kfs[c] || frames[c]->ctx != C || kfs[c]->ctx != C) return RSC_ERR_ARG;
+        if (kfs[c]->n && !already[c]) return RSC_ERR_ARG;
+        if (frames[c]->n && (!frame_mp[c] || !out[c])) return RSC_ERR_ARG;
+        if (check_orientation && !kfs[c]->has_angles) {
+            g_last_error = "orientation check on a KeyFrame view without angles (rsc_kfview_set_angles)";
+            return RSC_ERR_ARG;
+        }
+    }
+    // layout: problem table | already flags | frame_mp  (uploaded)  | windows | candidates | claims  (scratch)  |
+    // out | nmatches, rounds  (the part that comes back)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    std::vector<size_t> o_al(count), o_mp(count), o_rec(count), o_cd(count), o_cl(count), o_out(count), o_cnt(count);
+    int max_kf_points = 0;
+    size_t off = al(sizeof(FrameProjProblem) * count);
+    for (int c = 0; c < count; ++c) {
+        o_al[c] = off; off = al(off + (size_t)std::max(kfs[c]->n, 1));
+        o_mp[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
+    }
+    const size_t up = off;
+    for (int c = 0; c < count; ++c) {
+        o_rec[c] = off; off = al(off + sizeof(ProjRec) * (size_t)std::max(kfs[c]->n, 1));
+        o_cd[c] = off; off = al(off + sizeof(ProjCand) * (size_t)std::max(kfs[c]->n, 1));
+        max_kf_points = std::max(max_kf_points, kfs[c]->n);
+        o_cl[c] = off; off = al(off + 4 * (size_t)std::max(kfs[c]->n, 1));
+    }
+    const size_t back = off;
+    for (int c = 0; c < count; ++c) {
+        o_out[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
+        o_cnt[c] = off; off += 8;
+    }
+    const size_t bytes = al(off);
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = C->d_fp.ensure(bytes)) return e;
+    if (int e = C->h_fp.ensure(bytes)) return e;
+    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
+    char* h = C->h_fp.p;
+    char* d = C->d_fp.p;
+    for (int c = 0; c < count; ++c) {
+        const rsc_kfview& k = *kfs[c];
+        if (k.n) std::memcpy(h + o_al[c], already[c], (size_t)k.n);
+        if (frames[c]->n) std::memcpy(h + o_mp[c], frame_mp[c], 4 * (size_t)frames[c]->n);
+        FrameProjProblem p;
+        p.F = frames[c]->hdr;
+        p.K.mp_state = k.dev.mp_state;
+        p.K.mp_pos = k.dev.mp_pos;
+        p.K.mp_dmax = k.dev.mp_dmax;
+        p.K.mp_dmin = k.dev.mp_dmin;
+        p.K.mp_desc = reinterpret_cast<const ProjDesc*>(k.dev.mp_desc);
+        p.K.angle = k.has_angles ? k.d_angle.p : nullptr;
+        p.K.n = k.n;
+        std::memcpy(p.Tcw, Tcw + 16 * (size_t)c, sizeof(p.Tcw));
+        p.already = reinterpret_cast<const uint8_t*>(d + o_al[c]);
+        p.frame_mp = reinterpret_cast<const int32_t*>(d + o_mp[c]);
+        p.rec = reinterpret_cast<ProjRec*>(d + o_rec[c]);
+        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+        p.nmatches = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+        p.rounds = p.nmatches + 1;
+        std::memcpy(h + sizeof(FrameProjProblem) * c, &p, sizeof(p));
+    }
+    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
+    timing_begin(C, 3);
+    RSC_HIP(launch_search_by_projection(count, max_kf_points, reinterpret_cast<const FrameProjProblem*>(d), th,
+                                        orb_dist, check_orientation ? 1 : 0, C->stream));
+    timing_begin(C, 4);
+    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    if (C->timing) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
+        C->last_ms[2] = ms;
+    }
+    for (int c = 0; c < count; ++c) {
+        if (frames[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)frames[c]->n);
+        if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
+        if (rounds) std::memcpy(&rounds[c], h + o_cnt[c] + 4, 4);
+    }
+    return RSC_OK;
+}
+
+// Tracking::Relocalization's refinement chain (Tracking.cpp:1294-1323); each stage one launch over the
+// candidates still in the chain.
+int rsc_reloc_refine_many(rsc_context* C, rsc_frameview* const* frames, rsc_kfview* const* kfs, int count,
+                          const rsc_reloc_frame* fr, int32_t* const* frame_mp, const uint8_t* const* found,
+                          const int32_t* n_good_in, const float* Tcw_in, rsc_reloc_refine_result* out) {
+    if (!C || count < 0) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!frames || !kfs || !fr || !frame_mp || !found || !n_good_in || !Tcw_in || !out) return RSC_ERR_ARG;
+    for (int c = 0; c < count; ++c) {
+        if (!frames[c] || !kfs[c] || frames[c]->ctx != C || kfs[c]->ctx != C) return RSC_ERR_ARG;
+        if ((frames[c]->n && !frame_mp[c]) || (kfs[c]->n && !found[c])) return RSC_ERR_ARG;
+        for (int f = 0; f < frames[c]->n; ++f)
+            if (frame_mp[c][f] < -1 || frame_mp[c][f] >= kfs[c]->n) return RSC_ERR_ARG;
+        rsc_reloc_refine_result& r = out[c];
+        r.n_good = n_good_in[c];
+        r.n_additional[0] = r.n_additional[1] = -1;
+        r.pose_opts = 0;
+        std::memcpy(r.Tcw, Tcw_in + 16 * (size_t)c, sizeof(r.Tcw));
+    }
+    // SearchByProjection over the candidates in `sel` with sAlreadyFound = fnd[c]; the new matches are
+    // written to frame_mp (CurrentFrame.mvpMapPoints[bestIdx2] = pMP), nadd[c] = the return value
+    std::vector<int32_t> nadd(count, 0);
+    auto search = [&](const std::vector<int>& sel, const std::vector<const uint8_t*>& fnd, float th, int orb_dist) -> int {
+        const int m = (int)sel.size();
+        std::vector<rsc_frameview*> F(m);
+        std::vector<rsc_kfview*> K(m);
+        std::vector<float> T(16 * (size_t)m);
+        std::vector<const int32_t*> mp(m);
+        std::vector<std::vector<int32_t>> res(m);
+        std::vector<int32_t*> rp(m);
+        std::vector<int32_t> nm(m);
+        for (int q = 0; q < m; ++q) {
+            const int c = sel[q];
+            F[q] = frames[c];
+            K[q] = kfs[c];
+            std::memcpy(&T[16 * (size_t)q], out[c].Tcw, 16 * sizeof(float));
+            mp[q] = frame_mp[c];
+            res[q].assign((size_t)std::max(frames[c]->n, 1), -1);
+            rp[q] = res[q].data();
+        }
+        if (int st = rsc_search_by_projection_many(C, F.data(), K.data(), m, T.data(), fnd.data(), mp.data(), th,
+                                                   orb_dist, 1, rp.data(), nm.data(), nullptr))
+            return st;
+        for (int q = 0; q < m; ++q) {
+            const int c = sel[q];
+            for (int f = 0; f < frames[c]->n; ++f)
+                if (res[q][f] >= 0) frame_mp[c][f] = res[q][f];
+            nadd[c] = nm[q];
+        }
+        return RSC_OK;
+    };
+    // PoseOptimization(&mCurrentFrame) over the candidates in `sel`, on every occupied slot
+    auto optimise = [&](const std::vector<int>& sel, bool null_outliers) -> int {
+        const int m = (int)sel.size();
+        std::vector<std::vector<uint8_t>> has(m), outl(m);
+        std::vector<std::vector<float>> Xw(m), inv(m);
+        std::vector<rsc_poseopt_problem> pr(m);
+        std::vector<rsc_poseopt_result> res(m);
+        std::vector<uint8_t*> op(m);
+        for (int q = 0; q < m; ++q) {
+            const int c = sel[q];
+            const rsc_frameview& F = *frames[c];
+            const rsc_kfview& K = *kfs[c];
+            const size_t n = (size_t)F.n;
+            has[q].assign(std::max(n, (size_t)1), 0);
+            outl[q].assign(std::max(n, (size_t)1), 0);
+            Xw[q].assign(3 * std::max(n, (size_t)1), 0.f);
+            inv[q].assign(std::max(n, (size_t)1), 0.f);
+            for (size_t f = 0; f < n; ++f) {
+                const int32_t s = frame_mp[c][f];
+                if (s < 0) continue;
+                has[q][f] = 1;
+                for (int k = 0; k < 3; ++k) Xw[q][3 * f + k] = K.mp_pos[3 * (size_t)s + k];
+                inv[q][f] = F.inv_level_sigma2[F.octave[f]];
+            }
+            rsc_poseopt_problem& P = pr[q];
+            P.n = F.n;
+            P.has_mp = has[q].data();
+            P.uv = F.kp.data();
+            P.Xw = Xw[q].data();
+            P.inv_sigma2 = inv[q].data();
+            P.u_right = fr[c].u_right;
+            P.fx = F.K[0]; P.fy = F.K[1]; P.cx = F.K[2]; P.cy = F.K[3];
+            std::memcpy(P.Tcw, out[c].Tcw, sizeof(P.Tcw));
+            P.bf = fr[c].bf;
+            op[q] = outl[q].data();
+        }
+        if (int st = rsc_pose_optimization_many(C, pr.data(), m, res.data(), op.data())) return st;
+        for (int q = 0; q < m; ++q) {
+            const int c = sel[q];
+            out[c].n_good = res[q].n_good;
+            std::memcpy(out[c].Tcw, res[q].Tcw, sizeof(out[c].Tcw));
+            out[c].pose_opts++;
+            if (null_outliers)  // :1317-1319
+                for (int f = 0; f < frames[c]->n; ++f)
+                    if (has[q][f] && outl[q][f]) frame_mp[c][f] = -1;
+        }
+        return RSC_OK;
+    };
+    std::vector<int> s1, s2, s3, s4;
+    std::vector<const uint8_t*> f1;
+    for (int c = 0; c < count; ++c)
+        if (out[c].n_good < 50) {  // :1294
+            s1.push_back(c);
+            f1.push_back(found[c]);
+        }
+    if (s1.empty()) return RSC_OK;
+    if (int st = search(s1, f1, 10.0f, 100)) return st;  // :1296
+    for (int c : s1) {
+        out[c].n_additional[0] = nadd[c];
+        if (nadd[c] + out[c].n_good >= 50) s2.push_back(c);  // :1298
+    }
+    if (s2.empty()) return RSC_OK;
+    if (int st = optimise(s2, false)) return st;  // :1300
+    std::vector<std::vector<uint8_t>> found2;
+    for (int c : s2)
+        if (out[c].n_good > 30 && out[c].n_good < 50) {  // :1304
+            s3.push_back(c);
+            std::vector<uint8_t> fnd((size_t)std::max(kfs[c]->n, 1), 0);  // :1306-1309
+            for (int f = 0; f < frames[c]->n; ++f)
+                if (frame_mp[c][f] >= 0) fnd[frame_mp[c][f]] = 1;
+            found2.push_back(std::move(fnd));
+        }
+    if (s3.empty()) return RSC_OK;
+    std::vector<const uint8_t*> f3;
+    for (const auto& v : found2) f3.push_back(v.data());
+    if (int st = search(s3, f3, 3.0f, 64)) return st;  // :1310
+    for (int c : s3) {
+        out[c].n_additional[1] = nadd[c];
+        if (out[c].n_good + nadd[c] >= 50) s4.push_back(c);  // :1313
+    }
+    if (s4.empty()) return RSC_OK;
+    return optimise(s4, true);  // :1315-1319
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3098,9 +3425,22 @@ int rsc_loop_events_shared(rsc_sim3* const* solvers, const int32_t* event_begin,
 // mTcw = the RANSAC pose, :1268-1284), nGood < 10 -> the next success of the round (:1286-1287),
 // nGood >= 50 -> match (:1327-1331), otherwise SearchByProjection's turn (handed off).  The gate
 // passes of all events run as one rsc_pose_optimization_many each.
-int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events,
-                           const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
-                           rsc_reloc_gate_result* per_event, uint8_t* const* outlier, uint8_t* const* inliers) {
+//
+// rsc_reloc_events_refined is the same loop with `refine` set: a success with 10 <= nGood < 50 goes
+// through the SearchByProjection chain (rsc_reloc_refine_many over the events of the pass) and is a match
+// when that leaves nGood >= 50; otherwise the walk continues with the event's next success (:1327-1333).
+namespace {
+struct RelocRefine {
+    const rsc_reloc_candidate* cands;
+    rsc_frameview* const* views;
+    rsc_reloc_refined_result* per_event;
+    int32_t* const* frame_mp_out;
+};
+
+int reloc_events_gated_impl(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events,
+                            const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
+                            rsc_reloc_gate_result* per_event, uint8_t* const* outlier, uint8_t* const* inliers,
+                            const RelocRefine* refine) {
     if (n_events <= 0) return RSC_OK;
     if (!solvers || !event_begin || !frames || !per_candidate || !per_event) return RSC_ERR_ARG;
     const int total = event_begin[n_events];
@@ -3207,6 +3547,12 @@ int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, 
                 op[q] = jobs[q].outl.data();
             }
             if (int st = rsc_pose_optimization_many(C, pr.data(), (int)pr.size(), res.data(), op.data())) return st;
+            struct Chain {
+                size_t q;  // its job
+                std::vector<int32_t> mp;
+                std::vector<uint8_t> found;
+            };
+            std::vector<Chain> chains;
             for (size_t q = 0; q < jobs.size(); ++q) {
                 const Job& j = jobs[q];
                 rsc_reloc_gate_result& g = per_event[j.e];
@@ -3215,6 +3561,35 @@ int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, 
                 if (nGood < 10) {  // Tracking.cpp:1286-1287: continue with the next candidate
                     g.rejected++;
                     continue;
+                }
+                if (refine) {
+                    // mvpMapPoints after :1289-1291 as KeyFrame slots, and sFound (:1278, every inlier)
+                    const rsc_pnp* s = solvers[j.i];
+                    const rsc_reloc_candidate& cd = refine->cands[j.i];
+                    Chain ch;
+                    ch.q = q;
+                    ch.mp.assign((size_t)std::max(s->st.N_points, 1), -1);
+                    ch.found.assign((size_t)std::max(cd.kf->n, 1), 0);
+                    for (int c = 0; c < s->st.N; ++c) {
+                        const int slot = s->st.kp_index[c];
+                        if (!mask[j.i][slot]) continue;
+                        const int32_t ks = cd.matches[slot];
+                        if (ks < 0 || ks >= cd.kf->n) {
+                            g_last_error = "a RANSAC inlier's Frame slot has no KeyFrame slot in the candidate's matches";
+                            return RSC_ERR_ARG;
+                        }
+                        ch.found[ks] = 1;
+                        if (!j.outl[slot]) ch.mp[slot] = ks;
+                    }
+                    rsc_reloc_refined_result& x = refine->per_event[j.e];
+                    if (nGood < 50) {  // :1294: the chain decides
+                        chains.push_back(std::move(ch));
+                        continue;
+                    }
+                    x.n_good_first = nGood;
+                    x.n_additional[0] = x.n_additional[1] = -1;
+                    if (refine->frame_mp_out && refine->frame_mp_out[j.e])
+                        std::memcpy(refine->frame_mp_out[j.e], ch.mp.data(), 4 * (size_t)s->st.N_points);
                 }
                 g.status = nGood >= 50 ? RSC_GATE_MATCH : RSC_GATE_HANDOFF;
                 g.winner = j.i - event_begin[j.e];
@@ -3228,6 +3603,55 @@ int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, 
                 if (inliers && inliers[j.e]) std::memcpy(inliers[j.e], mask[j.i].data(), (size_t)nf);
                 resolved[j.e] = 1;
             }
+            if (!chains.empty()) {  // Tracking.cpp:1294-1323 on this pass's successes with 10 <= nGood < 50
+                const size_t m = chains.size();
+                std::vector<rsc_frameview*> F(m);
+                std::vector<rsc_kfview*> K(m);
+                std::vector<rsc_reloc_frame> fr(m);
+                std::vector<int32_t*> mp(m);
+                std::vector<const uint8_t*> fnd(m);
+                std::vector<int32_t> ng(m);
+                std::vector<float> T(16 * m);
+                std::vector<rsc_reloc_refine_result> rr(m);
+                for (size_t k = 0; k < m; ++k) {
+                    const Job& j = jobs[chains[k].q];
+                    F[k] = refine->views[j.e];
+                    K[k] = refine->cands[j.i].kf;
+                    fr[k] = frames[j.e];
+                    mp[k] = chains[k].mp.data();
+                    fnd[k] = chains[k].found.data();
+                    ng[k] = res[chains[k].q].n_good;
+                    std::memcpy(&T[16 * k], res[chains[k].q].Tcw, 16 * sizeof(float));
+                }
+                if (int st = rsc_reloc_refine_many(C, F.data(), K.data(), (int)m, fr.data(), mp.data(), fnd.data(),
+                                                   ng.data(), T.data(), rr.data()))
+                    return st;
+                for (size_t k = 0; k < m; ++k) {
+                    const Job& j = jobs[chains[k].q];
+                    rsc_reloc_gate_result& g = per_event[j.e];
+                    rsc_reloc_refined_result& x = refine->per_event[j.e];
+                    x.chains++;
+                    if (rr[k].n_good < 50) {  // :1327 fails: the next success of the round
+                        g.rejected++;
+                        continue;
+                    }
+                    g.status = RSC_GATE_MATCH;
+                    g.winner = j.i - event_begin[j.e];
+                    g.round = round;
+                    g.hypothesis = per_candidate[j.i].iterations - 1 - start_it[j.i];
+                    g.n_inliers = per_candidate[j.i].n_inliers;
+                    g.n_good = rr[k].n_good;
+                    std::memcpy(g.Tcw, rr[k].Tcw, sizeof(g.Tcw));
+                    x.n_good_first = ng[k];
+                    x.n_additional[0] = rr[k].n_additional[0];
+                    x.n_additional[1] = rr[k].n_additional[1];
+                    const int nf = solvers[j.i]->st.N_points;
+                    if (refine->frame_mp_out && refine->frame_mp_out[j.e])
+                        std::memcpy(refine->frame_mp_out[j.e], chains[k].mp.data(), 4 * (size_t)nf);
+                    if (inliers && inliers[j.e]) std::memcpy(inliers[j.e], mask[j.i].data(), (size_t)nf);
+                    resolved[j.e] = 1;
+                }
+            }
         }
         for (int e = 0; e < n_events; ++e) {  // nCandidates == 0: the while loop ends (:1239)
             if (resolved[e]) continue;
@@ -3235,6 +3659,54 @@ int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, 
             for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) any_active |= !discarded[i];
             if (!any_active) resolved[e] = 1;
         }
+    }
+    return RSC_OK;
+}
+}  // namespace
+
+int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events,
+                           const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
+                           rsc_reloc_gate_result* per_event, uint8_t* const* outlier, uint8_t* const* inliers) {
+    return reloc_events_gated_impl(solvers, event_begin, n_events, frames, per_candidate, per_event, outlier,
+                                   inliers, nullptr);
+}
+
+int rsc_reloc_events_refined(rsc_pnp* const* solvers, const rsc_reloc_candidate* candidates,
+                             const int32_t* event_begin, int n_events, rsc_frameview* const* views,
+                             const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
+                             rsc_reloc_refined_result* per_event, int32_t* const* frame_mp_out) {
+    if (n_events <= 0) return RSC_OK;
+    if (!solvers || !candidates || !event_begin || !views || !frames || !per_candidate || !per_event)
+        return RSC_ERR_ARG;
+    for (int e = 0; e < n_events; ++e) {
+        if (event_begin[e + 1] < event_begin[e] || event_begin[e] < 0) return RSC_ERR_ARG;
+        if (event_begin[e + 1] > event_begin[e] && !views[e]) return RSC_ERR_ARG;
+        for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
+            if (!solvers[i] || !candidates[i].kf || !candidates[i].matches) return RSC_ERR_ARG;
+            if (solvers[i]->st.N_points != views[e]->n || candidates[i].kf->ctx != solvers[i]->ctx ||
+                views[e]->ctx != solvers[i]->ctx)
+                return RSC_ERR_ARG;
+            if (!candidates[i].kf->has_angles) return RSC_ERR_ARG;  // matcher2(0.9, true) checks orientation
+        }
+        std::memset(&per_event[e], 0, sizeof(per_event[e]));
+        per_event[e].n_additional[0] = per_event[e].n_additional[1] = -1;
+    }
+    std::vector<rsc_reloc_gate_result> g((size_t)n_events);
+    const RelocRefine rf{candidates, views, per_event, frame_mp_out};
+    const int st = reloc_events_gated_impl(solvers, event_begin, n_events, frames, per_candidate, g.data(), nullptr,
+                                           nullptr, &rf);
+    if (st) return st;
+    for (int e = 0; e < n_events; ++e) {
+        rsc_reloc_refined_result& x = per_event[e];
+        x.status = g[e].status;
+        x.winner = g[e].winner;
+        x.round = g[e].round;
+        x.hypothesis = g[e].hypothesis;
+        x.n_inliers = g[e].n_inliers;
+        x.n_good = g[e].n_good;
+        x.rejected = g[e].rejected;
+        x.gates = g[e].gates;
+        std::memcpy(x.Tcw, g[e].Tcw, sizeof(x.Tcw));
     }
     return RSC_OK;
 }

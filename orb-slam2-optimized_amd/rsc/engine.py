@@ -53,6 +53,8 @@ EXPORTED = [
     "rsc_pnp_bind_stream", "rsc_sim3_bind_stream", "rsc_mlpnp_bind_stream", "rsc_reloc_events_shared",
     "rsc_loop_events_shared", "rsc_reloc_events_gated", "rsc_loop_events_gated",
     "rsc_diag_mlpnp_phase_stamps",
+    "rsc_frameview_create", "rsc_frameview_destroy", "rsc_kfview_set_angles", "rsc_search_by_projection_many",
+    "rsc_reloc_refine_many", "rsc_reloc_events_refined",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -71,6 +73,34 @@ class RelocGateResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("winner", C.c_int32), ("round", C.c_int32), ("hypothesis", C.c_int32),
                 ("n_inliers", C.c_int32), ("n_good", C.c_int32), ("rejected", C.c_int32), ("gates", C.c_int32),
                 ("Tcw", C.c_float * 16)]
+
+
+class RelocRefineResult(C.Structure):
+    """rsc_reloc_refine_result (include/rsc.h)."""
+    _fields_ = [("n_good", C.c_int32), ("n_additional", C.c_int32 * 2), ("pose_opts", C.c_int32),
+                ("Tcw", C.c_float * 16)]
+
+
+class RelocCandidate(C.Structure):
+    _fields_ = [("kf", C.c_void_p), ("matches", C.c_void_p)]
+
+
+class RelocRefinedResult(C.Structure):
+    """rsc_reloc_refined_result (include/rsc.h)."""
+    _fields_ = [("status", C.c_int32), ("winner", C.c_int32), ("round", C.c_int32), ("hypothesis", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_good", C.c_int32), ("rejected", C.c_int32), ("gates", C.c_int32),
+                ("n_good_first", C.c_int32), ("n_additional", C.c_int32 * 2), ("chains", C.c_int32),
+                ("Tcw", C.c_float * 16)]
+
+
+class FrameFeatures(C.Structure):
+    """rsc_frame_features (include/rsc.h)."""
+    _fields_ = [("n", C.c_int32), ("kp", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p),
+                ("desc", C.c_void_p), ("cell_begin", C.c_void_p), ("cell_feat", C.c_void_p), ("min_x", C.c_float),
+                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("grid_w_inv", C.c_float),
+                ("grid_h_inv", C.c_float), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("scale_factors", C.c_void_p), ("n_levels", C.c_int32),
+                ("log_scale_factor", C.c_float)]
 
 
 class LoopCandidate(C.Structure):
@@ -174,6 +204,14 @@ class KFView:
         _check(load_library().rsc_kfview_create(ctx.h, C.byref(k), C.byref(h)), "rsc_kfview_create")
         self.h = h
 
+    def set_angles(self, angle):
+        """mvKeysUn[i].angle of the KeyFrame (the rotation check of SearchByProjection reads them)."""
+        a = np.ascontiguousarray(angle, np.float32)
+        if a.size != self.n:
+            raise ValueError(f"{self.n} angles expected, got {a.size}")
+        _check(load_library().rsc_kfview_set_angles(self.h, a if a.size else np.zeros(1, np.float32)),
+               "rsc_kfview_set_angles")
+
     def close(self):
         if getattr(self, "h", None):
             load_library().rsc_kfview_destroy(self.h)
@@ -181,6 +219,96 @@ class KFView:
 
     def __del__(self):
         self.close()
+
+
+def frame_features_struct(fr):
+    """(ctypes rsc_frame_features, keep-alive arrays) for a rsc.synth.ProjFrame-like object."""
+    from rsc import synth
+    keep = [np.ascontiguousarray(fr.kp, np.float32), np.ascontiguousarray(fr.octave, np.int32),
+            np.ascontiguousarray(fr.angle, np.float32), np.ascontiguousarray(fr.desc, np.uint8),
+            np.ascontiguousarray(fr.cell_begin, np.int32), np.ascontiguousarray(fr.cell_feat, np.int32),
+            synth.scale_factors()]
+    if keep[5].size == 0:
+        keep[5] = np.zeros(1, np.int32)
+    k = FrameFeatures()
+    k.n = int(fr.n)
+    k.kp, k.octave, k.angle, k.desc, k.cell_begin, k.cell_feat, k.scale_factors = (a.ctypes.data for a in keep)
+    k.min_x, k.max_x, k.min_y, k.max_y = fr.min_x, fr.max_x, fr.min_y, fr.max_y
+    k.grid_w_inv, k.grid_h_inv = float(synth.GRID_W_INV), float(synth.GRID_H_INV)
+    k.fx, k.fy, k.cx, k.cy = fr.fx, fr.fy, fr.cx, fr.cy
+    k.n_levels = len(keep[6])
+    k.log_scale_factor = float(synth.LOG_SCALE_FACTOR)
+    return k, keep
+
+
+class FrameView:
+    """The current Frame as SearchByProjection reads it, resident in HBM (rsc_frameview_create)."""
+
+    def __init__(self, ctx: Context, fr):
+        self.ctx, self.n = ctx, int(fr.n)
+        k, keep = frame_features_struct(fr)
+        h = C.c_void_p()
+        _check(load_library().rsc_frameview_create(ctx.h, C.byref(k), C.byref(h)), "rsc_frameview_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().rsc_frameview_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def _ptrs(arrays):
+    return (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+
+
+def _handles(views):
+    return (C.c_void_p * max(len(views), 1))(*[v.h.value for v in views])
+
+
+def search_by_projection_many(ctx: Context, frames, kfs, Tcw, already, frame_mp, th: float, orb_dist: int,
+                              check_orientation: bool = True):
+    """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1317-1444)
+    for each (FrameView, KFView, Tcw [4,4], already uint8 [kf n], frame_mp int32 [frame n]) in one launch.
+    Returns (list of out int32 [frame n] = KeyFrame slot of each new match or -1, nmatches int32[count],
+    rounds int32[count])."""
+    c = len(frames)
+    T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(c, 16)) if c else np.zeros((1, 16), np.float32)
+    al = [np.ascontiguousarray(a, np.uint8) if k.n else np.zeros(1, np.uint8) for a, k in zip(already, kfs)]
+    mp = [np.ascontiguousarray(a, np.int32) if f.n else np.zeros(1, np.int32) for a, f in zip(frame_mp, frames)]
+    out = [np.full(max(f.n, 1), -7, np.int32) for f in frames]
+    nm = np.zeros(max(c, 1), np.int32)
+    rounds = np.zeros(max(c, 1), np.int32)
+    _check(load_library().rsc_search_by_projection_many(ctx.h, _handles(frames), _handles(kfs), c, T, _ptrs(al),
+                                                        _ptrs(mp), float(th), int(orb_dist), int(check_orientation),
+                                                        _ptrs(out), nm, rounds), "rsc_search_by_projection_many")
+    return [o[:f.n] for o, f in zip(out, frames)], nm[:c], rounds[:c]
+
+
+def reloc_refine_many(ctx: Context, frames, kfs, fr, frame_mp, found, n_good_in, Tcw_in):
+    """Tracking::Relocalization's refinement chain (Tracking.cpp:1294-1323, rsc_reloc_refine_many) for each
+    candidate: fr[c] = (u_right float32 [frame n] or None, bf); frame_mp[c] int32 [frame n] (entry state,
+    not modified); found[c] uint8 [kf n]; n_good_in[c]; Tcw_in[c] [4,4].  Returns (RelocRefineResult
+    records, list of final frame_mp arrays)."""
+    c = len(frames)
+    rf = (RelocFrame * max(c, 1))()
+    keep = []
+    for e, (ur, bf) in enumerate(fr):
+        if ur is not None:
+            a = np.ascontiguousarray(ur, np.float32)
+            keep.append(a)
+            rf[e].u_right = a.ctypes.data
+        rf[e].bf = float(bf)
+    mp = [np.array(a, np.int32) if f.n else np.full(1, -1, np.int32) for a, f in zip(frame_mp, frames)]
+    fd = [np.ascontiguousarray(a, np.uint8) if k.n else np.zeros(1, np.uint8) for a, k in zip(found, kfs)]
+    ng = np.ascontiguousarray(n_good_in, np.int32).reshape(-1) if c else np.zeros(1, np.int32)
+    T = np.ascontiguousarray(np.asarray(Tcw_in, np.float32).reshape(c, 16)) if c else np.zeros((1, 16), np.float32)
+    res = (RelocRefineResult * max(c, 1))()
+    _check(load_library().rsc_reloc_refine_many(ctx.h, _handles(frames), _handles(kfs), c, rf, _ptrs(mp), _ptrs(fd),
+                                                ng, T, res), "rsc_reloc_refine_many")
+    return np.ctypeslib.as_array(res).copy()[:c], [m[:f.n] for m, f in zip(mp, frames)]
 
 
 class Sim3Search:
@@ -460,6 +588,18 @@ def load_library(path: str = LIB_PATH):
     L.rsc_loop_events.argtypes = [C.POINTER(vp), i32p, C.c_int, C.POINTER(Sim3Result), C.POINTER(EventResult)]
     L.rsc_reloc_events_gated.argtypes = [C.POINTER(vp), i32p, C.c_int, C.POINTER(RelocFrame), C.POINTER(PnPResult),
                                          C.POINTER(RelocGateResult), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rsc_frameview_create.argtypes = [vp, C.POINTER(FrameFeatures), C.POINTER(vp)]
+    L.rsc_frameview_destroy.argtypes = [vp]
+    L.rsc_kfview_set_angles.argtypes = [vp, f32p_]
+    L.rsc_search_by_projection_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_,
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_float, C.c_int,
+                                                C.c_int, C.POINTER(C.c_void_p), i32p, i32p]
+    L.rsc_reloc_refine_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(RelocFrame),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i32p, f32p_,
+                                        C.POINTER(RelocRefineResult)]
+    L.rsc_reloc_events_refined.argtypes = [C.POINTER(vp), C.POINTER(RelocCandidate), i32p, C.c_int, C.POINTER(vp),
+                                           C.POINTER(RelocFrame), C.POINTER(PnPResult),
+                                           C.POINTER(RelocRefinedResult), C.POINTER(C.c_void_p)]
     L.rsc_loop_events_gated.argtypes = [C.POINTER(vp), C.POINTER(LoopCandidate), i32p, C.c_int,
                                         C.POINTER(Sim3Result), C.POINTER(LoopGateResult), C.POINTER(C.c_void_p)]
     _lib = L
@@ -1002,6 +1142,39 @@ class EventBatch:
                "reloc_events_gated")
         return np.ctypeslib.as_array(res).copy(), [o[:n] for o, n in zip(outl, npts)], \
             [m[:n] for m, n in zip(inl, npts)]
+
+    def run_reloc_refined(self, views, frames, candidates):
+        """Relocalization events from the candidate solvers to bMatch (rsc_reloc_events_refined,
+        Tracking.cpp:1239-1335): the gate of run_reloc_gated with the SearchByProjection refinement inside.
+        views[e] = FrameView of the event's Frame; frames[e] = (u_right or None, bf); candidates[e][c] =
+        (KFView with angles, matches int32 [frame n] = vvpMapPointMatches as KeyFrame slots).  Returns
+        (per-event RelocRefinedResult records, the accepted success's mvpMapPoints per event as KeyFrame
+        slots of the winner, all -1 without a match)."""
+        assert self.kind == "pnp"
+        ne = len(self.events)
+        if len(frames) != ne or len(views) != ne or len(candidates) != ne or \
+                any(len(c) != len(ev) for c, ev in zip(candidates, self.events)):
+            raise ValueError("one view and frame per event, one (kf, matches) per candidate")
+        L = load_library()
+        fr = (RelocFrame * max(ne, 1))()
+        keep = []
+        for e, (ur, bf) in enumerate(frames):
+            if ur is not None:
+                a = np.ascontiguousarray(ur, np.float32)
+                keep.append(a)
+                fr[e].u_right = a.ctypes.data
+            fr[e].bf = float(bf)
+        flat = [c for cs in candidates for c in cs]
+        rc = (RelocCandidate * max(len(flat), 1))()
+        for k, (kv, m) in enumerate(flat):
+            a = np.ascontiguousarray(m, np.int32)
+            keep.append(a)
+            rc[k].kf, rc[k].matches = kv.h.value, a.ctypes.data
+        res = (RelocRefinedResult * max(ne, 1))()
+        mo = [np.full(max(v.n, 1), -1, np.int32) for v in views]
+        _check(L.rsc_reloc_events_refined(self.batch._h, rc, self.begin, ne, _handles(views), fr, self._cand, res,
+                                          _ptrs(mo)), "reloc_events_refined")
+        return np.ctypeslib.as_array(res).copy()[:ne], [m[:v.n] for m, v in zip(mo, views)]
 
     def run_loop_gated(self, candidates):
         """Loop-closure events with the reference's SearchBySim3 + OptimizeSim3 gate

@@ -828,3 +828,193 @@ def make_loop_gate_event(rng: np.random.Generator, cands, n_points: int = 700, n
             m12[i] = where2[int(mid)] if rng.random() < good else int(rng.choice(with_mp2))
         out.append((kf2, m12, sim3_pair_from_kfs(kf1, kf2, m12)))
     return kf1, out
+
+
+# ---- ORBmatcher::SearchByProjection(Frame, KeyFrame, sAlreadyFound, th, ORBdist) inputs -----------
+@dataclasses.dataclass
+class ProjFrame:
+    """The current Frame as the relocalization SearchByProjection reads it (rsc_frame_features)."""
+    n: int
+    kp: np.ndarray          # float32 [n,2] mvKeysUn[i].pt
+    octave: np.ndarray      # int32 [n]
+    angle: np.ndarray       # float32 [n] mvKeysUn[i].angle
+    desc: np.ndarray        # uint8 [n,32]
+    cell_begin: np.ndarray  # int32 [64*48+1]
+    cell_feat: np.ndarray   # int32 []
+    fx: float = float(FX)
+    fy: float = float(FY)
+    cx: float = float(CX)
+    cy: float = float(CY)
+    min_x: float = 0.0
+    max_x: float = float(WIDTH)
+    min_y: float = 0.0
+    max_y: float = float(HEIGHT)
+
+
+def make_proj_frame(kp, octave, angle, desc, **kw) -> ProjFrame:
+    kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 2)
+    begin, feat = build_grid(kp)
+    return ProjFrame(len(kp), kp, np.ascontiguousarray(octave, np.int32), np.ascontiguousarray(angle, np.float32),
+                     np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), begin, feat, **kw)
+
+
+@dataclasses.dataclass
+class ProjProblem:
+    """One SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) call."""
+    kf: Sim3KF              # with kf.angle float32 [n] (mvKeysUn[i].angle)
+    frame: ProjFrame
+    Tcw: np.ndarray         # float32 [4,4] CurrentFrame.mTcw
+    already: np.ndarray     # uint8 [kf.n] sAlreadyFound.count(vpMPs[i])
+    frame_mp: np.ndarray    # int32 [frame.n] KeyFrame slot held by CurrentFrame.mvpMapPoints[f], or -1
+    Tcw_true: np.ndarray    # float64 [4,4]
+    truth: np.ndarray       # int32 [frame.n] KeyFrame slot of the MapPoint the feature observes, -1 none
+
+
+def make_reloc_projection_problem(rng: np.random.Generator, n_kf: int, n_frame: int, pose_err: float = 0.002,
+                                  n_clusters: int = 5, crowding: int = 4, occupied_frac: float = 0.1,
+                                  already_frac: float = 0.1, bad_frac: float = 0.03, noise_px: float = 1.0,
+                                  mp_frac: float = 0.75, rot_deg: float = 20.0) -> ProjProblem:
+    """A KeyFrame view (n_kf slots, about mp_frac of them with a MapPoint) and a Frame view (n_frame
+    features) of one scene, the Frame pose with an error of pose_err (rad, and as many metres), a share
+    of Frame slots occupied before the call and a share of the KeyFrame's MapPoints already found.
+    Crowding: n_clusters groups of `crowding` MapPoints sit at (almost) one world position with (almost)
+    one descriptor and one octave, and the Frame shows `crowding` features around that projection whose
+    descriptors rank the same for every member — so the members all prefer the same features and the
+    greedy claim order decides who gets which."""
+    sf = scale_factors()
+    n_points = max(int(mp_frac * n_kf), n_clusters * crowding)
+    n_single = n_points - n_clusters * crowding
+    P = np.stack([rng.uniform(-2.5, 2.5, n_points), rng.uniform(-1.5, 1.5, n_points),
+                  rng.uniform(3, 10, n_points)], 1)
+    mp_desc = rng.integers(0, 256, (n_points, 32), dtype=np.uint8)
+    cluster_of = np.full(n_points, -1, np.int64)
+    for c in range(n_clusters):
+        mem = n_single + c * crowding + np.arange(crowding)
+        P[mem] = P[mem[0]] + rng.normal(0, 1e-3, (crowding, 3))
+        mp_desc[mem] = _flip(rng, np.repeat(mp_desc[mem[:1]], crowding, 0), 2.0)
+        cluster_of[mem] = c
+    Rk = random_rotation(rng, 0.05)
+    tk = rng.normal(0, 0.05, 3)
+    Xk = P @ Rk.T + tk
+    uvk = np.stack([FX * Xk[:, 0] / Xk[:, 2] + CX, FY * Xk[:, 1] / Xk[:, 2] + CY], 1)
+    visk = (Xk[:, 2] > 0.1) & (uvk[:, 0] >= 0) & (uvk[:, 0] < WIDTH) & (uvk[:, 1] >= 0) & (uvk[:, 1] < HEIGHT)
+    if int(visk.sum()) > n_kf:  # keep the crowded points, drop single ones
+        drop = np.nonzero(visk & (cluster_of < 0))[0][:int(visk.sum()) - n_kf]
+        P[drop, 2] = -5.0  # behind the KeyFrame: not observed by it
+        Xk = P @ Rk.T + tk
+        visk[drop] = False
+    kf = _make_kf(rng, P, mp_desc, Rk, tk, n_kf - int(visk.sum()), bad_frac, noise_px)
+    assert kf.n == n_kf
+    slot_of = np.full(n_points, -1, np.int64)
+    has = kf.mp_id >= 0
+    slot_of[kf.mp_id[has]] = np.nonzero(has)[0]
+    Ok = -Rk.T @ tk
+    for c in range(n_clusters):  # one octave per cluster
+        s = slot_of[cluster_of == c]
+        s = s[s >= 0]
+        o = int(rng.integers(1, N_LEVELS - 1))
+        kf.octave[s] = o
+        kf.mp_dmax[s] = (np.linalg.norm(P[kf.mp_id[s]] - Ok, axis=1) * sf[o]).astype(np.float32)
+        kf.mp_dmin[s] = (kf.mp_dmax[s] / sf[N_LEVELS - 1]).astype(np.float32)
+    kf.angle = rng.uniform(0, 360, n_kf).astype(np.float32)
+    # the Frame: a small motion from the KeyFrame
+    Rf = random_rotation(rng, 0.05) @ Rk
+    tf = tk + rng.normal(0, 0.05, 3)
+    Of = -Rf.T @ tf
+    Xf = P @ Rf.T + tf
+    uvf = np.stack([FX * Xf[:, 0] / Xf[:, 2] + CX, FY * Xf[:, 1] / Xf[:, 2] + CY], 1)
+    visf = (Xf[:, 2] > 0.1) & (uvf[:, 0] >= 2) & (uvf[:, 0] < WIDTH - 2) & (uvf[:, 1] >= 2) & (uvf[:, 1] < HEIGHT - 2)
+
+    def level_in_frame(j):  # MapPoint::PredictScale of point j from the Frame
+        s = slot_of[j]
+        if s < 0:
+            return int(rng.integers(0, N_LEVELS))
+        ratio = float(kf.mp_dmax[s]) / float(np.linalg.norm(P[j] - Of))
+        return int(np.clip(np.ceil(np.log(ratio) / np.log(1.2)), 0, N_LEVELS - 1))
+
+    kp, octv, ang, desc, src = [], [], [], [], []
+    for c in range(n_clusters):
+        mem = np.nonzero(cluster_of == c)[0]
+        j0 = mem[0]
+        if not visf[j0] or slot_of[j0] < 0:
+            continue
+        lvl = level_in_frame(j0)
+        a0 = float(kf.angle[slot_of[j0]])
+        for k in range(crowding):
+            kp.append(uvf[j0] + rng.uniform(-1.5, 1.5, 2))
+            octv.append(lvl)
+            ang.append((a0 + rot_deg + rng.normal(0, 2.0)) % 360.0)
+            desc.append(_flip(rng, mp_desc[j0:j0 + 1], 3.0 + 6.0 * k)[0])
+            src.append(int(slot_of[mem[k]]))
+    n_crowd = len(kp)
+    for j in rng.permutation(np.nonzero(visf & (cluster_of < 0))[0]):
+        if len(kp) >= max(n_crowd, int(0.85 * n_frame)):
+            break
+        kp.append(uvf[j] + rng.normal(0, noise_px, 2))
+        octv.append(int(np.clip(level_in_frame(j) + rng.choice([-1, 0, 0, 1]), 0, N_LEVELS - 1)))
+        s = slot_of[j]
+        a0 = float(kf.angle[s]) if s >= 0 else float(rng.uniform(0, 360))
+        wrong = rng.random() < 0.08  # a match the rotation check removes
+        ang.append(float(rng.uniform(0, 360)) if wrong else (a0 + rot_deg + rng.normal(0, 2.0)) % 360.0)
+        desc.append(_flip(rng, mp_desc[j:j + 1], 8.0)[0])
+        src.append(int(s))
+    kp, octv, ang, desc, src = kp[:n_frame], octv[:n_frame], ang[:n_frame], desc[:n_frame], src[:n_frame]
+    while len(kp) < n_frame:
+        kp.append(np.array([rng.uniform(0, WIDTH), rng.uniform(0, HEIGHT)]))
+        octv.append(int(rng.choice(N_LEVELS, p=level_probabilities())))
+        ang.append(float(rng.uniform(0, 360)))
+        desc.append(rng.integers(0, 256, 32, dtype=np.uint8))
+        src.append(-1)
+    perm = rng.permutation(n_frame)
+    kp = np.clip(np.array(kp)[perm], 0, [WIDTH - 1e-3, HEIGHT - 1e-3]).astype(np.float32)
+    frame = make_proj_frame(kp, np.array(octv)[perm], np.array(ang, np.float32)[perm], np.array(desc)[perm])
+    frame_mp = np.full(n_frame, -1, np.int32)
+    occ = rng.random(n_frame) < occupied_frac
+    frame_mp[occ] = rng.integers(0, n_kf, int(occ.sum()))
+    already = ((rng.random(n_kf) < already_frac) & has).astype(np.uint8)
+    T_true = np.eye(4)
+    T_true[:3, :3], T_true[:3, 3] = Rf, tf
+    Tcw = np.eye(4)
+    Tcw[:3, :3] = random_rotation(rng, pose_err) @ Rf
+    Tcw[:3, 3] = tf + rng.normal(0, pose_err, 3)
+    return ProjProblem(kf, frame, Tcw.astype(np.float32), already, frame_mp, T_true,
+                       np.array(src, np.int32)[perm])
+
+
+def restrict_kf(kf: Sim3KF, keep_slots) -> Sim3KF:
+    """A copy of the KeyFrame view that holds MapPoints only on keep_slots (a KeyFrame that shares little
+    with the Frame)."""
+    out = dataclasses.replace(kf, mp_state=np.zeros_like(kf.mp_state))
+    out.mp_state[keep_slots] = kf.mp_state[keep_slots]
+    out.angle = kf.angle
+    return out
+
+
+def make_reloc_refine_event(rng: np.random.Generator, n_kf: int, n_frame: int, cands, **kw):
+    """One Tracking::Relocalization() call whose candidates go through the SearchByProjection chain: one
+    scene (make_reloc_projection_problem, exact pose, nothing occupied) and per candidate (n_match,
+    n_wrong, n_mps) a KeyFrame view holding n_mps MapPoints seen by the Frame (None: all of them), BoW
+    matches vvpMapPointMatches = n_match correct (Frame slot -> KeyFrame slot) + n_wrong wrong ones, and
+    the PnP scene built from them.  Returns (problem, [(kf, matches int32 [n_frame], PnPScene)])."""
+    p = make_reloc_projection_problem(rng, n_kf, n_frame, pose_err=0.0, occupied_frac=0.0, already_frac=0.0,
+                                      bad_frac=0.0, **kw)
+    good = np.nonzero(p.truth >= 0)[0]
+    good = good[p.kf.mp_state[p.truth[good]] == 1]
+    s2 = level_sigma2()
+    out = []
+    for n_match, n_wrong, n_mps in cands:
+        fs = rng.permutation(good)
+        right, rest = fs[:n_match], fs[n_match:]
+        kf = p.kf if n_mps is None else restrict_kf(p.kf, p.truth[fs[:n_mps]])
+        matches = np.full(n_frame, -1, np.int32)
+        matches[right] = p.truth[right]
+        free = np.setdiff1d(np.arange(n_frame), right)
+        wrong = rng.permutation(free)[:n_wrong]
+        pool = np.setdiff1d(np.nonzero(kf.mp_state == 1)[0], p.truth[right])
+        matches[wrong] = rng.choice(pool, size=n_wrong, replace=False) if n_wrong else []
+        idx = np.sort(np.concatenate([right, wrong])).astype(np.int32)
+        sc = PnPScene(p2d=p.frame.kp[idx].copy(), p3dw=kf.mp_pos[matches[idx]].copy(),
+                      sigma2=s2[p.frame.octave[idx]].astype(np.float32), kp_index=idx, n_points=n_frame,
+                      R_true=p.Tcw_true[:3, :3], t_true=p.Tcw_true[:3, 3], inlier_true=np.isin(idx, right))
+        out.append((kf, matches, sc))
+    return p, out

@@ -1,0 +1,15 @@
+"""The SearchByProjection kernel (frameproj.hip) runs without a private segment: its rounds are a chain
+of dependent LDS / L2 accesses, and a stack round trip inside them would add to every round.  Reads the
+gfx950 code object inside librsc.so as tests/test_cpu_kernel_resources.py does (no GPU needed)."""
+from test_cpu_kernel_resources import _kernels
+
+
+def test_frameproj_kernel_has_no_scratch():
+    ks = _kernels()
+    hits = [n for n in ks if "frameproj_kernel" in n or "frameproj_setup_kernel" in n]
+    assert len(hits) == 2, f"frameproj kernels in librsc.so: {hits}"
+    for n in hits:
+        k = ks[n]
+        assert k[".private_segment_fixed_size"] == 0, (n, k[".private_segment_fixed_size"])
+        assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, n
+        assert k[".group_segment_fixed_size"] <= 64 * 1024, (n, k[".group_segment_fixed_size"])
