@@ -9,7 +9,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fa
            -fno-gpu-flush-denormals-to-zero -Wall -Wno-unused-function -Wno-unused-variable
 HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
-all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu facade_test facade_proj_test
+all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu facade_test facade_proj_test chase_mirror_test
 
 $(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
@@ -69,6 +69,20 @@ facade_proj_test: $(LIBDIR)/facade_proj_test
 $(LIBDIR)/facade_proj_test: tests/cpp/facade_proj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
 	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_proj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
 
+# TEST-ONLY host programs: tridiag_qr with and without the mirror() / any_lane() hooks of its
+# rotation sink (tests/test_cpu_chase_mirror.py); the second build runs under the host sanitizers
+chase_mirror_test: $(LIBDIR)/chase_mirror_test $(LIBDIR)/chase_mirror_test_san
+
+HOSTFLAGS = -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-unknown-pragmas
+
+$(LIBDIR)/chase_mirror_test: tests/cpp/chase_mirror_test.cpp $(CSRC)/rsc_core.h
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/chase_mirror_test_san: tests/cpp/chase_mirror_test.cpp $(CSRC)/rsc_core.h
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -81,4 +95,4 @@ frameproj_emu:
 clean:
 	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build
 
-.PHONY: all oracle hostemu frameproj_emu facade_test facade_proj_test clean
+.PHONY: all oracle hostemu frameproj_emu facade_test facade_proj_test chase_mirror_test clean

@@ -209,6 +209,25 @@ template <typename Q, typename = void>
 struct qr_has_sweep_end { static constexpr bool value = false; };
 template <typename Q>
 struct qr_has_sweep_end<Q, decltype((void)std::declval<Q&>().sweep_end())> { static constexpr bool value = true; };
+// Optional hook `q.mirror()`: a pointer to 2n - 1 doubles of the sink's own (LDS on the device, any
+// array on the host) that tridiag_qr keeps equal to (diag[0..n), sub[0..n-1)): it fills it once and
+// every rotation slot stores the entries it wrote (static addresses, in the shadow of the slot's
+// dependent chain), so that the top of a step reads diag[end-1], diag[end], sub[end-1], diag[start],
+// sub[start] at a per-lane address instead of by select chains over the register arrays.  Only an
+// entry the deflation test zeroed differs from its register (the mirror keeps the old value), and
+// those are never read: sub[end-1] and sub[start] are nonzero by the definition of end and start.
+template <typename Q, typename = void>
+struct qr_has_mirror { static constexpr bool value = false; };
+template <typename Q>
+struct qr_has_mirror<Q, decltype((void)std::declval<Q&>().mirror())> { static constexpr bool value = true; };
+// Optional hook `q.any_lane(p)`: whether p holds on any lane of the wave that is still iterating (on
+// the host: p itself).  With it the deflation tests and the nonzero mask of a step run only over the
+// ranges of entries below some lane's `end` (entries at or above `end` cannot change a lane's state:
+// every use of them is masked by i < end), one wave-uniform guard per range.
+template <typename Q, typename = void>
+struct qr_has_any_lane { static constexpr bool value = false; };
+template <typename Q>
+struct qr_has_any_lane<Q, decltype((void)std::declval<Q&>().any_lane(true))> { static constexpr bool value = true; };
 
 // Implicit symmetric QR iterations on (diag, sub) with the rotations handed to
 // `qapply(k, c, s, apply)` (which must perform Q = Q * G on columns k,k+1 when `apply`, and leave
@@ -218,6 +237,13 @@ struct qr_has_sweep_end<Q, decltype((void)std::declval<Q&>().sweep_end())> { sta
 // tridiag_qr reads diag[start], sub[start] by a select chain only when start > 0 (0: always).
 #ifndef RSC_QR_START0
 #define RSC_QR_START0 1
+#endif
+// tridiag_qr uses a sink's mirror() / any_lane() hooks (0: as a sink without them; A/B builds).
+#ifndef RSC_QR_MIRROR
+#define RSC_QR_MIRROR 1
+#endif
+#ifndef RSC_QR_TRIM
+#define RSC_QR_TRIM 1
 #endif
 // How often tridiag_qr tests for a non-finite block (steps; 1 = every step).
 #ifndef RSC_NAN_CHECK_EVERY
@@ -239,19 +265,45 @@ RSC_HD bool tridiag_qr(S (&diag)[n], S (&sub)[n - 1], QApply&& qapply, int (&per
     // combined with the non-short-circuit & and | (a short-circuit || is a branch again).
     // Single-exit loop (Eigen's two `break`s folded into `run`): with several exits the CFG
     // structurizer nests the loop and every lane pays for the extra control flow.
+    constexpr bool kMirror = RSC_QR_MIRROR && qr_has_mirror<QApply>::value;
+    constexpr bool kTrim = RSC_QR_TRIM && qr_has_any_lane<QApply>::value;
+    // entries per guarded range: a guard costs about as much as four entries' tests; 3, 4 and 6
+    // measured within 0.7 us of each other on the split eigen stage, 3 ahead
+    constexpr int kTrimRange = 3;
+    S* mir = nullptr;
+    if constexpr (kMirror) {
+        mir = qapply.mirror();
+        RSC_UNROLL for (int i = 0; i < n; ++i) mir[i] = diag[i];
+        RSC_UNROLL for (int i = 0; i < n - 1; ++i) mir[n + i] = sub[i];
+    }
     bool run = true;
     while (run) {
         // for (i = start; i < end; ++i): |sub| < considerAsZero, or (sub/eps)^2 <= |d_i| + |d_i+1|
-        RSC_UNROLL for (int i = 0; i < n - 1; ++i) {
-            const S scaled = precision_inv * sub[i];
-            const bool z = (int)(rabs(sub[i]) < considerAsZero) | (int)(scaled * scaled <= (rabs(diag[i]) + rabs(diag[i + 1])));
-            sub[i] = (z & (i >= start) & (i < end)) ? S(0) : sub[i];
-        }
         // The two searches on a bit mask of the nonzero sub-diagonal entries (a find-last-set instead
         // of an 11-step select chain each):
         // while (end > 0 && sub[end-1] == 0) end--;  ->  end = 1 + last nonzero index below end, or 0
         unsigned nz = 0u;
-        RSC_UNROLL for (int i = 0; i < n - 1; ++i) nz |= (sub[i] != S(0)) ? (1u << i) : 0u;
+        if constexpr (kTrim) {
+            // ranges of entries at or above every lane's `end` are skipped: their deflation is masked
+            // by i < end, and their bits of nz (left 0) by the masks of live and zero
+            RSC_UNROLL for (int r = 0; r < n - 1; r += kTrimRange) {
+                if (r == 0 || qapply.any_lane(end > r)) {
+                    RSC_UNROLL for (int i = r; i < (r + kTrimRange < n - 1 ? r + kTrimRange : n - 1); ++i) {
+                        const S scaled = precision_inv * sub[i];
+                        const bool z = (int)(rabs(sub[i]) < considerAsZero) | (int)(scaled * scaled <= (rabs(diag[i]) + rabs(diag[i + 1])));
+                        sub[i] = (z & (i >= start) & (i < end)) ? S(0) : sub[i];
+                        nz |= (sub[i] != S(0)) ? (1u << i) : 0u;
+                    }
+                }
+            }
+        } else {
+            RSC_UNROLL for (int i = 0; i < n - 1; ++i) {
+                const S scaled = precision_inv * sub[i];
+                const bool z = (int)(rabs(sub[i]) < considerAsZero) | (int)(scaled * scaled <= (rabs(diag[i]) + rabs(diag[i + 1])));
+                sub[i] = (z & (i >= start) & (i < end)) ? S(0) : sub[i];
+            }
+            RSC_UNROLL for (int i = 0; i < n - 1; ++i) nz |= (sub[i] != S(0)) ? (1u << i) : 0u;
+        }
         const unsigned live = nz & ((1u << end) - 1u);
         end = live ? 32 - __builtin_clz(live) : 0;
         run = end > 0;
@@ -284,31 +336,40 @@ RSC_HD bool tridiag_qr(S (&diag)[n], S (&sub)[n - 1], QApply&& qapply, int (&per
 #endif
         // ---- tridiagonal_qr_step(diag, sub, start, end) ----
         S dEm1 = S(0), dE = S(0), eE = S(0), dS = S(0), zS = S(0);
-        RSC_UNROLL for (int j = 1; j < n; ++j) {
-            const bool m = j == end;
-            dEm1 = m ? diag[j - 1] : dEm1;
-            dE = m ? diag[j] : dE;
-            eE = m ? sub[j - 1] : eE;
-        }
+        if constexpr (kMirror) {
+            // 1 <= end <= n - 1 and 0 <= start < end: five reads at per-lane addresses
+            dEm1 = mir[end - 1];
+            dE = mir[end];
+            eE = mir[n + end - 1];
+            dS = mir[start];
+            zS = mir[n + start];
+        } else {
+            RSC_UNROLL for (int j = 1; j < n; ++j) {
+                const bool m = j == end;
+                dEm1 = m ? diag[j - 1] : dEm1;
+                dE = m ? diag[j] : dE;
+                eE = m ? sub[j - 1] : eE;
+            }
 #if RSC_QR_START0
-        // start is 0 until a sub-diagonal entry above the bottom block deflates: the select chain
-        // runs behind a branch that a wave skips while none of its lanes has start > 0
-        dS = diag[0];
-        zS = sub[0];
-        if (__builtin_expect(start != 0, 0)) {
-            RSC_UNROLL for (int j = 1; j < n - 1; ++j) {
+            // start is 0 until a sub-diagonal entry above the bottom block deflates: the select chain
+            // runs behind a branch that a wave skips while none of its lanes has start > 0
+            dS = diag[0];
+            zS = sub[0];
+            if (__builtin_expect(start != 0, 0)) {
+                RSC_UNROLL for (int j = 1; j < n - 1; ++j) {
+                    const bool m = j == start;
+                    dS = m ? diag[j] : dS;
+                    zS = m ? sub[j] : zS;
+                }
+            }
+#else
+            RSC_UNROLL for (int j = 0; j < n - 1; ++j) {
                 const bool m = j == start;
                 dS = m ? diag[j] : dS;
                 zS = m ? sub[j] : zS;
             }
-        }
-#else
-        RSC_UNROLL for (int j = 0; j < n - 1; ++j) {
-            const bool m = j == start;
-            dS = m ? diag[j] : dS;
-            zS = m ? sub[j] : zS;
-        }
 #endif
+        }
         // Wilkinson shift; the three cases of Eigen are evaluated side by side and selected
         // (td == 0: mu - |e|; e^2 underflows: the two-quotient form; otherwise e^2/(td +- h))
         const S td = (dEm1 - dE) * S(0.5);
@@ -334,6 +395,7 @@ RSC_HD bool tridiag_qr(S (&diag)[n], S (&sub)[n - 1], QApply&& qapply, int (&per
                 diag[k] = c * (c * diag[k] - s * sub[k]) - s * (c * sub[k] - s * diag[k + 1]);
                 diag[k + 1] = s * sdk + c * dkp1;
                 sub[k] = c * sdk - s * dkp1;
+                if constexpr (kMirror) mir[n + k] = sub[k];  // (stored here: one register copy fewer in two slots)
                 if (k > 0) sub[k - 1] = (k > start) ? c * sub[k - 1] - s * z : sub[k - 1];
                 x = sub[k];
                 if (k < n - 2) {
@@ -345,6 +407,13 @@ RSC_HD bool tridiag_qr(S (&diag)[n], S (&sub)[n - 1], QApply&& qapply, int (&per
                 // conditional call here gets tail-duplicated into the loop latch, which turns
                 // the QR loop into a nested loop that serialises the lanes of a wave)
                 qapply(k, c, s, !(c == S(1) && s == S(0)));
+                // the slot's stores of the mirror: every entry the slot wrote (sub[k] above), except
+                // sub[k+1], which the lane's next slot rewrites and stores (m above)
+                if constexpr (kMirror) {
+                    mir[k] = diag[k];
+                    mir[k + 1] = diag[k + 1];
+                    if (k > 0) mir[n + k - 1] = sub[k - 1];
+                }
             }
         }
         if constexpr (qr_has_sweep_end<QApply>::value) qapply.sweep_end();

@@ -680,7 +680,10 @@ constexpr int kSplitUnits = 4;     // chase / row wave pairs per workgroup (one 
 constexpr int kSplitRowLanes = 3;  // row-wave lanes per hypothesis (4 rows of Q each)
 constexpr int kRingPar = 24;       // doubles per parity in E: (c, s) of slots 0..10, then the step word
 constexpr int kRingPerm = 48;      // E[48..49]: the four sorted column indices (int32)
-constexpr int kSplitDsub = 24;     // doubles per hypothesis of the (diag, sub) slab
+// doubles per hypothesis of the (diag, sub) slab (23 used); the chase lanes read it at per-lane
+// indices (tridiag_qr's mirror): 25 doubles = 50 banks' width, so the 20 lanes of a unit start on
+// 20 different bank pairs (24 put them on four)
+constexpr int kSplitDsub = 25;
 constexpr int kSplitHyps = kSplitUnits * 20;
 
 // s_sleep argument between polls of a pub / ack flag (0: poll back to back)
@@ -735,6 +738,14 @@ struct SplitRing {
         const int need = (int)seq - 1;
         split_wait(ack, fault, [need](int v) { return v >= need; });
     }
+};
+
+// The ring of the batched split eigen stage: as SplitRing, plus tridiag_qr's mirror() and any_lane()
+// hooks.  The mirror is the hypothesis' own (diag, sub) slab, free once the chase lane has loaded it.
+struct SplitRingMirror : SplitRing {
+    double* dsub;  // this hypothesis' slab: diag[0..12), sub[0..11)
+    RSC_HD double* mirror() const { return dsub; }
+    __device__ __forceinline__ bool any_lane(bool p) const { return __builtin_amdgcn_ballot_w64(p) != 0; }
 };
 
 // ---- The Refine's 12x12 eigenvectors in the split form (one problem, two waves) ----
@@ -997,7 +1008,7 @@ __device__ __forceinline__ void pnp_eig_split_body(const DevPnP* __restrict__ pr
         RSC_UNROLL for (int i = 0; i < 12; ++i) diag[i] = ds[i];
         RSC_UNROLL for (int i = 0; i < 11; ++i) sub[i] = ds[12 + i];
         int perm[12];
-        SplitRing ring{E, pub + unit, ack + unit, fault};
+        SplitRingMirror ring{{E, pub + unit, ack + unit, fault}, Du + lane * kSplitDsub};
         tridiag_qr<double, 12>(diag, sub, ring, perm);
         int32_t* pm = reinterpret_cast<int32_t*>(E + kRingPerm);
         RSC_UNROLL for (int c = 0; c < 4; ++c) pm[c] = perm[c];
