@@ -589,6 +589,75 @@ int rsc_reloc_events_refined(rsc_pnp* const* solvers, const rsc_reloc_candidate*
                              const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
                              rsc_reloc_refined_result* per_event, int32_t* const* frame_mp_out);
 
+/* ---- The loop-closing projection matchers over a flat MapPoint list ------------------------------
+ * ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cpp:241-352) and
+ * ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:823-946): the two matcher calls of
+ * LoopClosing::ComputeSim3 (LoopClosing.cpp:360) and LoopClosing::SearchAndFuse (:578-600) over
+ * mvpLoopMapPoints.  Every point that passes the gates (depth z >= 0, KeyFrame::IsInImage with the
+ * maximum excluded, 0.8 dmin <= dist <= 1.2 dmax, PO.Pn >= 0.5 dist) takes the keypoint of the predicted
+ * levels [L-1, L] with the smallest descriptor distance (<= TH_LOW = 50) inside th * scale[L] of its
+ * projection.  SearchByProjection skips keypoints whose vpMatched slot is set, by the caller or by an
+ * earlier point of the call (the reference's sequential order is reproduced exactly); Fuse skips none. */
+typedef struct {
+    int32_t n;             /* vpPoints.size() */
+    const uint8_t* state;  /* [n] 1 = good, 2 = isBad() */
+    const float* pos;      /* [n][3] GetWorldPos() */
+    const float* normal;   /* [n][3] GetNormal() */
+    const float* dmax;     /* [n] mfMaxDistance */
+    const float* dmin;     /* [n] mfMinDistance */
+    const uint8_t* desc;   /* [n][32] GetDescriptor() */
+} rsc_mappoints;
+typedef struct rsc_mpview rsc_mpview;
+/* Upload a MapPoint list to HBM once; the view is shared by the projection call and by every Fuse call of
+ * a loop correction.  Precondition: the points are distinct MapPoints (the reference builds
+ * mvpLoopMapPoints through mnLoopPointForKF, LoopClosing.cpp:350-353, which guarantees it). */
+int rsc_mpview_create(rsc_context* ctx, const rsc_mappoints* points, rsc_mpview** out);
+void rsc_mpview_destroy(rsc_mpview* view);
+
+/* SearchByProjection(pKF = kfs[c], Scw[c], vpPoints = points[c], vpMatched, th) for c < count in one launch
+ * (one workgroup per problem).  Scw [count][16] row-major: the Isometry3f as the reference passes it; with
+ * mScw = Converter::toIso(g2o::Sim3) that is the unit rotation and the translation NOT divided by the
+ * scale, and the matcher uses both as they are (Ow = -R^T t), which this call keeps.
+ * already[c][i] (points[c] n entries): spAlreadyFound.count(vpPoints[i]), the point is in vpMatched on
+ * entry.  occupied[c][idx] (kfs[c] n entries): vpMatched[idx] != NULL on entry.  out[c][idx]: index into
+ * points[c] of the MapPoint the call writes to vpMatched[idx], else -1; nmatches[c] = the return value;
+ * rounds (may be NULL): fixed-point rounds run (diagnostic).  A KeyFrame with n > 8192 is RSC_ERR_ARG.
+ * Camera z == 0 is defined: the projection is inf / NaN, IsInImage is false, the point is skipped. */
+int rsc_search_by_projection_kf_many(rsc_context* ctx, rsc_kfview* const* kfs, rsc_mpview* const* points, int count,
+                                     const float* Scw, const uint8_t* const* already,
+                                     const uint8_t* const* occupied, int th, int32_t* const* out,
+                                     int32_t* nmatches, int32_t* rounds);
+
+/* Fuse(pKF = kfs[c], Scw[c], vpPoints = points, th, vpReplacePoint) for c < count in one launch, one lane
+ * per (point, KeyFrame) pair.  Scw [count][16] row-major with linear() = s * R; the call divides by
+ * scw = sqrt(row0 . row0) as the reference does.  in_kf[c][i] (points n entries):
+ * pKF->GetMapPoints().count(vpPoints[i]).  best_idx[c][i]: bestIdx when bestDist <= 50, else -1; the
+ * caller does the bookkeeping of :930-940 from the KeyFrame's own slot (replace, or AddObservation /
+ * AddMapPoint).  nfused[c] = the return value (the number of best_idx[c][i] >= 0). */
+int rsc_fuse_sim3_many(rsc_context* ctx, rsc_kfview* const* kfs, int count, rsc_mpview* points, const float* Scw,
+                       const uint8_t* const* in_kf, float th, int32_t* const* best_idx, int32_t* nfused);
+
+/* The closing stage of LoopClosing::ComputeSim3 (LoopClosing.cpp:318-320, :360-370) on the result of
+ * rsc_loop_events_gated, for `count` accepted events in one launch: gSmw from kf_matched's pose,
+ * mg2oScw = gScm * gSmw, mScw = toIso(mg2oScw), SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints,
+ * mvpCurrentMatchedPoints, 10), nTotalMatches >= 40.  The composition is host arithmetic in double
+ * (csrc/rsc_sim3compose.h; its parity with the reference binary is unpinned). */
+typedef struct {
+    int32_t accepted;    /* nTotalMatches >= 40 */
+    int32_t n_projected; /* SearchByProjection's return value */
+    int32_t n_total;     /* nTotalMatches */
+    double Scw_sim3[8];  /* mg2oScw: q (x, y, z, w), t, s */
+    float Scw[16];       /* mScw, row-major */
+} rsc_loop_verify_result;
+/* S [count][8]: rsc_loop_gate_result.S.  matches[c] (kf_cur[c] n entries): matches_out of the gate; a slot
+ * is occupied when matches[c][idx] != -1 (-2, a MapPoint not in the matched KeyFrame, is a non-null
+ * pointer).  already[c][i] (loop_points[c] n entries): the point is in mvpCurrentMatchedPoints.
+ * projected (may be NULL / NULL entries): [kf_cur n] as `out` of rsc_search_by_projection_kf_many. */
+int rsc_loop_verify_many(rsc_context* ctx, rsc_kfview* const* kf_cur, rsc_kfview* const* kf_matched,
+                         rsc_mpview* const* loop_points, int count, const double* S,
+                         const int32_t* const* matches, const uint8_t* const* already,
+                         rsc_loop_verify_result* out, int32_t* const* projected);
+
 /* ---- KeyFrameDatabase: BoW candidate scoring (src/KeyFrameDatabase.cpp) ---------------------- */
 /* A device-resident keyframe database: each KeyFrame is a slot in [0, capacity) holding its
  * BowVector (word ids ascending, TF-IDF values, DBoW2 L1_NORM scoring), its

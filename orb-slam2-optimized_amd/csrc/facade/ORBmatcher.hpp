@@ -243,6 +243,54 @@ FrameViewUpload upload_frameview(const FrameT& F) {
 
 }  // namespace detail
 
+// mvpLoopMapPoints uploaded once (rsc_mpview_create) and shared by the projection call of
+// LoopClosing::ComputeSim3 and every Fuse call of LoopClosing::SearchAndFuse.  The points must be distinct
+// and non-null (LoopClosing.cpp:350-353 guarantees both).  MapPoint additionally needs GetNormal().
+template <class MPPtr>
+class LoopMapPoints {
+public:
+    explicit LoopMapPoints(const std::vector<MPPtr>& vpPoints) : pts(vpPoints) {
+        const size_t n = pts.size();
+        std::vector<uint8_t> state(n, 2), desc(32 * n, 0);
+        std::vector<float> pos(3 * n, 0.f), nrm(3 * n, 0.f), dmax(n, 0.f), dmin(n, 0.f);
+        for (size_t i = 0; i < n; ++i) {
+            if (!pts[i]) throw std::runtime_error("rsc: LoopMapPoints: null MapPoint");
+            auto& mp = *pts[i];
+            if (mp.isBad()) continue;
+            state[i] = 1;
+            const auto X = mp.GetWorldPos();
+            const auto N = mp.GetNormal();
+            for (int c = 0; c < 3; ++c) {
+                pos[3 * i + c] = X(c);
+                nrm[3 * i + c] = N(c);
+            }
+            dmax[i] = detail::mp_max_distance(mp);
+            dmin[i] = detail::mp_min_distance(mp);
+            const auto d = mp.GetDescriptor();
+            const uint8_t* dr = d.template ptr<uint8_t>(0);
+            std::copy(dr, dr + 32, desc.begin() + 32 * i);
+        }
+        rsc_mappoints m;
+        m.n = (int32_t)n;
+        m.state = state.data();
+        m.pos = pos.data();
+        m.normal = nrm.data();
+        m.dmax = dmax.data();
+        m.dmin = dmin.data();
+        m.desc = desc.data();
+        check(rsc_mpview_create(thread_context(), &m, &h), "rsc_mpview_create");
+    }
+    LoopMapPoints(const LoopMapPoints&) = delete;
+    LoopMapPoints& operator=(const LoopMapPoints&) = delete;
+    ~LoopMapPoints() { rsc_mpview_destroy(h); }
+    rsc_mpview* handle() const { return h; }
+    const std::vector<MPPtr>& points() const { return pts; }
+
+private:
+    std::vector<MPPtr> pts;
+    rsc_mpview* h = nullptr;
+};
+
 class ORBmatcher {
 public:
     // ORBmatcher::ORBmatcher (ORBmatcher.cpp:12; defaults include/ORBmatcher.hpp:35)
@@ -494,7 +542,183 @@ public:
         return std::vector<int>(nm.begin(), nm.begin() + C);
     }
 
+    // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cpp:241-352; LoopClosing.cpp:360):
+    // the points that are not bad and not already in vpMatched are projected with Scw (an Isometry3f:
+    // rotation() / translation(), used as they are) and matched to the keypoints of pKF whose vpMatched slot
+    // is empty; the new matches are written to vpMatched, returns their number.
+    template <class KFPtr, class IsoT, class MPPtr>
+    int SearchByProjection(KFPtr pKF, const IsoT& Scw, const std::vector<MPPtr>& vpPoints,
+                           std::vector<MPPtr>& vpMatched, int th) {
+        LoopMapPoints<MPPtr> pts(vpPoints);
+        std::vector<KFPtr> k(1, pKF);
+        std::vector<IsoT> s(1, Scw);
+        std::vector<const LoopMapPoints<MPPtr>*> p(1, &pts);
+        std::vector<std::vector<MPPtr>*> m(1, &vpMatched);
+        return SearchByProjectionMany(k, s, p, m, th)[0];
+    }
+
+    // SearchByProjection(vpKFs[c], Scw[c], *points[c], *vpMatched[c], th) for several problems in one launch
+    // over prepared point views.  Each KeyFrame object is uploaded once.
+    template <class KFPtr, class IsoT, class MPPtr>
+    std::vector<int> SearchByProjectionMany(const std::vector<KFPtr>& vpKFs, const std::vector<IsoT>& Scw,
+                                            const std::vector<const LoopMapPoints<MPPtr>*>& points,
+                                            const std::vector<std::vector<MPPtr>*>& vpMatched, int th) {
+        const int C = (int)vpKFs.size();
+        std::vector<detail::KFViewUpload> views;
+        std::vector<int> ki;
+        upload_distinct(vpKFs, views, ki);
+        std::vector<rsc_kfview*> hk(C);
+        std::vector<rsc_mpview*> hp(C);
+        std::vector<float> T(16 * (size_t)(C > 0 ? C : 1), 0.f);
+        std::vector<std::vector<uint8_t>> already(C), occ(C);
+        std::vector<std::vector<int32_t>> out(C);
+        std::vector<const uint8_t*> pal(C), pocc(C);
+        std::vector<int32_t*> pout(C);
+        for (int c = 0; c < C; ++c) {
+            hk[c] = views[ki[c]].h;
+            hp[c] = points[c]->handle();
+            iso_to_array(Scw[c], &T[16 * (size_t)c]);
+            const std::vector<MPPtr>& pts = points[c]->points();
+            const std::vector<MPPtr>& m = *vpMatched[c];
+            std::set<MPPtr> found(m.begin(), m.end());  // spAlreadyFound (:255-256)
+            found.erase(nullptr);
+            const int nk = views[ki[c]].n;
+            already[c].assign(pts.size() > 0 ? pts.size() : 1, 0);
+            for (size_t i = 0; i < pts.size(); ++i) already[c][i] = found.count(pts[i]) ? 1 : 0;
+            occ[c].assign((size_t)(nk > 0 ? nk : 1), 0);
+            for (int i = 0; i < nk && (size_t)i < m.size(); ++i) occ[c][i] = m[i] ? 1 : 0;
+            out[c].assign((size_t)(nk > 0 ? nk : 1), -1);
+            pal[c] = already[c].data();
+            pocc[c] = occ[c].data();
+            pout[c] = out[c].data();
+        }
+        std::vector<int32_t> nm(C > 0 ? C : 1, 0);
+        check(rsc_search_by_projection_kf_many(thread_context(), hk.data(), hp.data(), C, T.data(), pal.data(),
+                                               pocc.data(), th, pout.data(), nm.data(), nullptr),
+              "SearchByProjection(KeyFrame, Scw, vpPoints)");
+        for (int c = 0; c < C; ++c) {  // vpMatched[bestIdx] = pMP (:345)
+            std::vector<MPPtr>& m = *vpMatched[c];
+            const std::vector<MPPtr>& pts = points[c]->points();
+            for (int i = 0; i < views[ki[c]].n && (size_t)i < m.size(); ++i)
+                if (out[c][i] >= 0) m[i] = pts[out[c][i]];
+        }
+        return std::vector<int>(nm.begin(), nm.begin() + C);
+    }
+
+    // Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cpp:823-946; LoopClosing.cpp:593): Scw carries
+    // s * R in rotation().  KeyFrame additionally needs GetMapPoints(), GetMapPoint(idx) and
+    // AddMapPoint(pMP, idx); MapPoint AddObservation(pKF, idx).
+    template <class KFPtr, class IsoT, class MPPtr>
+    int Fuse(KFPtr pKF, const IsoT& Scw, const std::vector<MPPtr>& vpPoints, float th,
+             std::vector<MPPtr>& vpReplacePoint) {
+        LoopMapPoints<MPPtr> pts(vpPoints);
+        std::vector<KFPtr> k(1, pKF);
+        std::vector<IsoT> s(1, Scw);
+        std::vector<std::vector<MPPtr>*> r(1, &vpReplacePoint);
+        return FuseMany(k, s, pts, th, r)[0];
+    }
+
+    // Fuse(vpKFs[c], Scw[c], points, th, *vpReplacePoints[c]) for every corrected KeyFrame of
+    // LoopClosing::SearchAndFuse (:578-600) in one launch against one prepared point view.  Fuse's points
+    // are independent of each other, so the device projects every (point, KeyFrame) pair at once and the
+    // bookkeeping of :930-940 runs afterwards, KeyFrame by KeyFrame in the reference's order.  What the
+    // reference reads from the map between two Fuse calls is read at that moment here too: after_kf(c) is
+    // called when KeyFrame c is done (SearchAndFuse runs its pRep->Replace loop there), and the bookkeeping
+    // of the next KeyFrame tests spAlreadyFound (:851) against its GetMapPoints() as they are then and reads
+    // GetMapPoint(bestIdx) then.  A point that a Replace put into a later KeyFrame is therefore skipped for
+    // it, as in the reference; the return values count what the bookkeeping kept.  Not re-read: isBad() of
+    // the loop points (Replace never changes it for them).
+    template <class KFPtr, class IsoT, class MPPtr>
+    std::vector<int> FuseMany(const std::vector<KFPtr>& vpKFs, const std::vector<IsoT>& Scw,
+                              const LoopMapPoints<MPPtr>& points, float th,
+                              const std::vector<std::vector<MPPtr>*>& vpReplacePoints) {
+        return FuseMany(vpKFs, Scw, points, th, vpReplacePoints, [](int) {});
+    }
+
+    template <class KFPtr, class IsoT, class MPPtr, class AfterKF>
+    std::vector<int> FuseMany(const std::vector<KFPtr>& vpKFs, const std::vector<IsoT>& Scw,
+                              const LoopMapPoints<MPPtr>& points, float th,
+                              const std::vector<std::vector<MPPtr>*>& vpReplacePoints, AfterKF after_kf) {
+        const int C = (int)vpKFs.size();
+        std::vector<detail::KFViewUpload> views;
+        std::vector<int> ki;
+        upload_distinct(vpKFs, views, ki);
+        const std::vector<MPPtr>& pts = points.points();
+        const size_t np = pts.size();
+        std::vector<rsc_kfview*> hk(C);
+        std::vector<float> T(16 * (size_t)(C > 0 ? C : 1), 0.f);
+        std::vector<std::vector<uint8_t>> in_kf(C);
+        std::vector<std::vector<int32_t>> best(C);
+        std::vector<const uint8_t*> pin(C);
+        std::vector<int32_t*> pbest(C);
+        for (int c = 0; c < C; ++c) {
+            hk[c] = views[ki[c]].h;
+            iso_to_array(Scw[c], &T[16 * (size_t)c]);
+            const auto found = vpKFs[c]->GetMapPoints();  // spAlreadyFound (:839)
+            in_kf[c].assign(np > 0 ? np : 1, 0);
+            for (size_t i = 0; i < np; ++i) in_kf[c][i] = found.count(pts[i]) ? 1 : 0;
+            best[c].assign(np > 0 ? np : 1, -1);
+            pin[c] = in_kf[c].data();
+            pbest[c] = best[c].data();
+        }
+        std::vector<int32_t> nf(C > 0 ? C : 1, 0);
+        check(rsc_fuse_sim3_many(thread_context(), hk.data(), C, points.handle(), T.data(), pin.data(), th,
+                                 pbest.data(), nf.data()),
+              "Fuse(KeyFrame, Scw, vpPoints)");
+        for (int c = 0; c < C; ++c) {
+            std::vector<MPPtr>& rep = *vpReplacePoints[c];
+            const auto found = vpKFs[c]->GetMapPoints();  // spAlreadyFound as it is now (:839)
+            int kept = 0;
+            for (size_t i = 0; i < np; ++i) {
+                const int idx = best[c][i];
+                if (idx < 0) continue;
+                if (!in_kf[c][i] && found.count(pts[i])) continue;  // joined the KeyFrame since the launch (:851)
+                ++kept;
+                MPPtr pMPinKF = vpKFs[c]->GetMapPoint(idx);  // :930
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad() && i < rep.size()) rep[i] = pMPinKF;  // :933-934
+                } else {
+                    pts[i]->AddObservation(vpKFs[c], idx);  // :938-939
+                    vpKFs[c]->AddMapPoint(pts[i], idx);
+                }
+            }
+            nf[c] = kept;
+            after_kf(c);
+        }
+        return std::vector<int>(nf.begin(), nf.begin() + C);
+    }
+
 private:
+    // one upload per distinct KeyFrame object; ki[c] = its view
+    template <class KFPtr>
+    static void upload_distinct(const std::vector<KFPtr>& vpKFs, std::vector<detail::KFViewUpload>& views,
+                                std::vector<int>& ki) {
+        std::vector<const void*> keys;
+        ki.assign(vpKFs.size(), 0);
+        for (size_t c = 0; c < vpKFs.size(); ++c) {
+            size_t j = 0;
+            for (; j < keys.size(); ++j)
+                if (keys[j] == (const void*)&*vpKFs[c]) break;
+            if (j == keys.size()) {
+                keys.push_back((const void*)&*vpKFs[c]);
+                views.push_back(detail::upload_kfview(vpKFs[c], vpKFs[c]->GetMapPointMatches()));
+            }
+            ki[c] = (int)j;
+        }
+    }
+
+    template <class IsoT>
+    static void iso_to_array(const IsoT& S, float* T) {
+        const auto R = S.rotation();
+        const auto t = S.translation();
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) T[4 * r + k] = R(r, k);
+            T[4 * r + 3] = t(r);
+        }
+        T[12] = T[13] = T[14] = 0.f;
+        T[15] = 1.f;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 };

@@ -25,6 +25,8 @@
 #include "rsc_orbmatch.h"
 #include "rsc_sim3match.h"
 #include "rsc_frameproj.h"
+#include "rsc_kfproj.h"
+#include "rsc_sim3compose.h"
 #include "rsc_kfdb.h"
 
 using namespace rsc;
@@ -3917,6 +3919,258 @@ int rsc_loop_events_gated(rsc_sim3* const* solvers, const rsc_loop_candidate* ca
             resolved[e] = 1;
         }
         if (int st = refill(again)) return st;
+    }
+    return RSC_OK;
+}
+
+// ---- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and Fuse(pKF, Scw, vpPoints, th, ...) (rsc_kfproj.h) ----
+struct rsc_mpview {
+    rsc_context* ctx = nullptr;
+    int n = 0;
+    DevBuf<char> mem;  // state | pos | normal | dmax | dmin | desc
+    DevKfpPoints dev;  // device pointers
+};
+
+int rsc_mpview_create(rsc_context* C, const rsc_mappoints* p, rsc_mpview** out) {
+    if (!C || !p || !out) return RSC_ERR_ARG;
+    *out = nullptr;
+    if (p->n < 0) return RSC_ERR_ARG;
+    if (p->n > 0 && (!p->state || !p->pos || !p->normal || !p->dmax || !p->dmin || !p->desc)) return RSC_ERR_ARG;
+    const size_t n = (size_t)p->n;
+    S3Blob b;
+    const size_t o_st = b.add(p->state, n), o_pos = b.add(p->pos, 12 * n), o_nrm = b.add(p->normal, 12 * n);
+    const size_t o_mx = b.add(p->dmax, 4 * n), o_mn = b.add(p->dmin, 4 * n), o_d = b.add(p->desc, 32 * n);
+    b.reserve(256);  // n == 0: a non-empty allocation
+    std::unique_ptr<rsc_mpview> v(new rsc_mpview);
+    v->ctx = C;
+    v->n = p->n;
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = v->mem.ensure(b.h.size())) return e;
+    char* d = v->mem.p;
+    v->dev.state = reinterpret_cast<const uint8_t*>(d + o_st);
+    v->dev.pos = reinterpret_cast<const float*>(d + o_pos);
+    v->dev.normal = reinterpret_cast<const float*>(d + o_nrm);
+    v->dev.dmax = reinterpret_cast<const float*>(d + o_mx);
+    v->dev.dmin = reinterpret_cast<const float*>(d + o_mn);
+    v->dev.desc = reinterpret_cast<const ProjDesc*>(d + o_d);
+    v->dev.n = p->n;
+    RSC_HIP(hipMemcpy(d, b.h.data(), b.h.size(), hipMemcpyHostToDevice));
+    *out = v.release();
+    return RSC_OK;
+}
+
+void rsc_mpview_destroy(rsc_mpview* v) {
+    if (!v) return;
+    (void)hipStreamSynchronize(v->ctx->stream);
+    delete v;
+}
+
+namespace {
+DevKfpKF kfp_kf_of(const rsc_kfview& k) {
+    DevKfpKF K;
+    K.kp = reinterpret_cast<const ProjPt*>(k.dev.kp);
+    K.octave = k.dev.octave;
+    K.desc = reinterpret_cast<const ProjDesc*>(k.dev.desc);
+    K.cell_begin = k.dev.cell_begin;
+    K.cell_feat = k.dev.cell_feat;
+    K.scale = k.dev.scale;
+    K.min_x = k.dev.min_x; K.max_x = k.dev.max_x; K.min_y = k.dev.min_y; K.max_y = k.dev.max_y;
+    K.gw_inv = k.dev.gw_inv; K.gh_inv = k.dev.gh_inv;
+    K.fx = k.dev.fx; K.fy = k.dev.fy; K.cx = k.dev.cx; K.cy = k.dev.cy;
+    K.log_sf = k.dev.log_sf;
+    K.n = k.dev.n;
+    K.n_levels = k.dev.n_levels;
+    return K;
+}
+
+int kfp_check_kf(const rsc_context* C, const rsc_kfview* k) {
+    if (!k || k->ctx != C) return RSC_ERR_ARG;
+    if (k->n > kKfpMaxKeypoints) {
+        g_last_error = "KeyFrame with more than 8192 keypoints";
+        return RSC_ERR_ARG;
+    }
+    if (k->dev.n_levels > 64) return RSC_ERR_ARG;  // the level field of the cached window
+    return 0;
+}
+}  // namespace
+
+int rsc_search_by_projection_kf_many(rsc_context* C, rsc_kfview* const* kfs, rsc_mpview* const* points, int count,
+                                     const float* Scw, const uint8_t* const* already,
+                                     const uint8_t* const* occupied, int th, int32_t* const* out,
+                                     int32_t* nmatches, int32_t* rounds) {
+    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!kfs || !points || !Scw || !already || !occupied || !out) return RSC_ERR_ARG;
+    for (int c = 0; c < count; ++c) {
+        if (int e = kfp_check_kf(C, kfs[c])) return e;
+        if (!points[c] || points[c]->ctx != C) return RSC_ERR_ARG;
+        if (points[c]->n && !already[c]) return RSC_ERR_ARG;
+        if (kfs[c]->n && (!occupied[c] || !out[c])) return RSC_ERR_ARG;
+    }
+    // layout: problem table | already flags | occupied flags  (uploaded)  | windows | candidates | claims
+    // (scratch)  | out | nmatches, rounds  (the part that comes back)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    std::vector<size_t> o_al(count), o_oc(count), o_rec(count), o_cd(count), o_cl(count), o_out(count), o_cnt(count);
+    int max_points = 0;
+    size_t off = al(sizeof(KfProjProblem) * count);
+    for (int c = 0; c < count; ++c) {
+        o_al[c] = off; off = al(off + (size_t)std::max(points[c]->n, 1));
+        o_oc[c] = off; off = al(off + (size_t)std::max(kfs[c]->n, 1));
+    }
+    const size_t up = off;
+    for (int c = 0; c < count; ++c) {
+        const size_t np = (size_t)std::max(points[c]->n, 1);
+        o_rec[c] = off; off = al(off + sizeof(ProjRec) * np);
+        o_cd[c] = off; off = al(off + sizeof(ProjCand) * np);
+        o_cl[c] = off; off = al(off + 4 * np);
+        max_points = std::max(max_points, points[c]->n);
+    }
+    const size_t back = off;
+    for (int c = 0; c < count; ++c) {
+        o_out[c] = off; off = al(off + 4 * (size_t)std::max(kfs[c]->n, 1));
+        o_cnt[c] = off; off += 8;
+    }
+    const size_t bytes = al(off);
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = C->d_fp.ensure(bytes)) return e;
+    if (int e = C->h_fp.ensure(bytes)) return e;
+    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
+    char* h = C->h_fp.p;
+    char* d = C->d_fp.p;
+    for (int c = 0; c < count; ++c) {
+        const rsc_kfview& k = *kfs[c];
+        const rsc_mpview& m = *points[c];
+        if (m.n) std::memcpy(h + o_al[c], already[c], (size_t)m.n);
+        if (k.n) std::memcpy(h + o_oc[c], occupied[c], (size_t)k.n);
+        KfProjProblem p;
+        p.K = kfp_kf_of(k);
+        p.P = m.dev;
+        std::memcpy(p.Scw, Scw + 16 * (size_t)c, sizeof(p.Scw));
+        p.already = reinterpret_cast<const uint8_t*>(d + o_al[c]);
+        p.occupied = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
+        p.rec = reinterpret_cast<ProjRec*>(d + o_rec[c]);
+        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+        p.nmatches = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+        p.rounds = p.nmatches + 1;
+        std::memcpy(h + sizeof(KfProjProblem) * c, &p, sizeof(p));
+    }
+    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
+    timing_begin(C, 3);
+    RSC_HIP(launch_search_by_projection_kf(count, max_points, reinterpret_cast<const KfProjProblem*>(d), (float)th,
+                                           C->stream));
+    timing_begin(C, 4);
+    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    if (C->timing) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
+        C->last_ms[2] = ms;
+    }
+    for (int c = 0; c < count; ++c) {
+        if (kfs[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)kfs[c]->n);
+        if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
+        if (rounds) std::memcpy(&rounds[c], h + o_cnt[c] + 4, 4);
+    }
+    return RSC_OK;
+}
+
+int rsc_fuse_sim3_many(rsc_context* C, rsc_kfview* const* kfs, int count, rsc_mpview* points, const float* Scw,
+                       const uint8_t* const* in_kf, float th, int32_t* const* best_idx, int32_t* nfused) {
+    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!kfs || !points || points->ctx != C || !Scw || !in_kf || !best_idx) return RSC_ERR_ARG;
+    const int np = points->n;
+    for (int c = 0; c < count; ++c) {
+        if (int e = kfp_check_kf(C, kfs[c])) return e;
+        if (np && (!in_kf[c] || !best_idx[c])) return RSC_ERR_ARG;
+    }
+    // layout: problem table | in_kf flags  (uploaded)  | best_idx  (comes back)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t row = al((size_t)std::max(np, 1)), row4 = al(4 * (size_t)std::max(np, 1));
+    const size_t o_in = al(sizeof(KfFuseProblem) * count);
+    const size_t back = o_in + row * (size_t)count;
+    const size_t bytes = back + row4 * (size_t)count;
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = C->d_fp.ensure(bytes)) return e;
+    if (int e = C->h_fp.ensure(bytes)) return e;
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    char* h = C->h_fp.p;
+    char* d = C->d_fp.p;
+    for (int c = 0; c < count; ++c) {
+        if (np) std::memcpy(h + o_in + row * c, in_kf[c], (size_t)np);
+        KfFuseProblem p;
+        p.K = kfp_kf_of(*kfs[c]);
+        std::memcpy(p.Scw, Scw + 16 * (size_t)c, sizeof(p.Scw));
+        p.in_kf = reinterpret_cast<const uint8_t*>(d + o_in + row * c);
+        p.best_idx = reinterpret_cast<int32_t*>(d + back + row4 * c);
+        std::memcpy(h + sizeof(KfFuseProblem) * c, &p, sizeof(p));
+    }
+    RSC_HIP(hipMemcpyAsync(d, h, back, hipMemcpyHostToDevice, C->stream));
+    timing_begin(C, 3);
+    RSC_HIP(launch_fuse_sim3(count, &points->dev, np, reinterpret_cast<const KfFuseProblem*>(d), th, C->stream));
+    timing_begin(C, 4);
+    if (np) RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    if (C->timing) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
+        C->last_ms[2] = ms;
+    }
+    for (int c = 0; c < count; ++c) {
+        const int32_t* b = reinterpret_cast<const int32_t*>(h + back + row4 * c);
+        int nf = 0;
+        for (int i = 0; i < np; ++i) {
+            best_idx[c][i] = b[i];
+            nf += b[i] >= 0;
+        }
+        if (nfused) nfused[c] = nf;
+    }
+    return RSC_OK;
+}
+
+// LoopClosing.cpp:318-320 and :360-370 (rsc_sim3compose.h)
+int rsc_loop_verify_many(rsc_context* C, rsc_kfview* const* kf_cur, rsc_kfview* const* kf_matched,
+                         rsc_mpview* const* loop_points, int count, const double* S,
+                         const int32_t* const* matches, const uint8_t* const* already,
+                         rsc_loop_verify_result* res, int32_t* const* projected) {
+    if (!C || count < 0) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!kf_cur || !kf_matched || !loop_points || !S || !matches || !already || !res) return RSC_ERR_ARG;
+    std::vector<float> Scw(16 * (size_t)count);
+    std::vector<std::vector<uint8_t>> occ(count);
+    std::vector<std::vector<int32_t>> outs(count);
+    std::vector<const uint8_t*> occp(count);
+    std::vector<int32_t*> outp(count);
+    std::vector<int32_t> nm(count);
+    for (int c = 0; c < count; ++c) {
+        if (!kf_cur[c] || !kf_matched[c] || kf_matched[c]->ctx != C) return RSC_ERR_ARG;
+        const int n = kf_cur[c]->n;
+        if (n && !matches[c]) return RSC_ERR_ARG;
+        const SoSim3 gScm = sc_sim3_from_array(S + 8 * (size_t)c);
+        const SoSim3 gSmw = sc_sim3_from_pose(kf_matched[c]->R, kf_matched[c]->t);  // :318
+        const SoSim3 gScw = sc_compose(gScm, gSmw);                                  // :319
+        sc_sim3_to_array(gScw, res[c].Scw_sim3);
+        sc_to_iso(gScw, res[c].Scw);                                                 // :320
+        std::memcpy(&Scw[16 * (size_t)c], res[c].Scw, sizeof(res[c].Scw));
+        occ[c].assign((size_t)std::max(n, 1), 0);
+        for (int i = 0; i < n; ++i) occ[c][i] = matches[c][i] != -1;  // -2 is a non-null pointer
+        outs[c].assign((size_t)std::max(n, 1), -1);
+        occp[c] = occ[c].data();
+        outp[c] = outs[c].data();
+    }
+    if (int st = rsc_search_by_projection_kf_many(C, kf_cur, loop_points, count, Scw.data(), already, occp.data(),
+                                                  10, outp.data(), nm.data(), nullptr))  // :360
+        return st;
+    for (int c = 0; c < count; ++c) {
+        const int n = kf_cur[c]->n;
+        int total = nm[c];
+        for (int i = 0; i < n; ++i) total += occ[c][i];  // :363-368
+        res[c].n_projected = nm[c];
+        res[c].n_total = total;
+        res[c].accepted = total >= 40;  // :370
+        if (projected && projected[c] && n) std::memcpy(projected[c], outs[c].data(), 4 * (size_t)n);
     }
     return RSC_OK;
 }

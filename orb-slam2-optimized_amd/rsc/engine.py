@@ -55,6 +55,8 @@ EXPORTED = [
     "rsc_diag_mlpnp_phase_stamps",
     "rsc_frameview_create", "rsc_frameview_destroy", "rsc_kfview_set_angles", "rsc_search_by_projection_many",
     "rsc_reloc_refine_many", "rsc_reloc_events_refined",
+    "rsc_mpview_create", "rsc_mpview_destroy", "rsc_search_by_projection_kf_many", "rsc_fuse_sim3_many",
+    "rsc_loop_verify_many",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -285,6 +287,92 @@ def search_by_projection_many(ctx: Context, frames, kfs, Tcw, already, frame_mp,
                                                         _ptrs(mp), float(th), int(orb_dist), int(check_orientation),
                                                         _ptrs(out), nm, rounds), "rsc_search_by_projection_many")
     return [o[:f.n] for o, f in zip(out, frames)], nm[:c], rounds[:c]
+
+
+class MapPointsStruct(C.Structure):
+    """rsc_mappoints (include/rsc.h)."""
+    _fields_ = [("n", C.c_int32), ("state", C.c_void_p), ("pos", C.c_void_p), ("normal", C.c_void_p),
+                ("dmax", C.c_void_p), ("dmin", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class LoopVerifyResult(C.Structure):
+    """rsc_loop_verify_result (include/rsc.h)."""
+    _fields_ = [("accepted", C.c_int32), ("n_projected", C.c_int32), ("n_total", C.c_int32),
+                ("Scw_sim3", C.c_double * 8), ("Scw", C.c_float * 16)]
+
+
+class MPView:
+    """A flat list of distinct MapPoints (mvpLoopMapPoints) resident in HBM (rsc_mpview_create): an object
+    with n, state uint8 [n], pos / normal float32 [n,3], dmax / dmin float32 [n], desc uint8 [n,32]."""
+
+    def __init__(self, ctx: Context, pts):
+        self.ctx, self.n = ctx, int(pts.n)
+        pad = lambda a, dt, k: (np.ascontiguousarray(a, dt).reshape(-1) if self.n else np.zeros(k, dt))
+        keep = [pad(pts.state, np.uint8, 1), pad(pts.pos, np.float32, 3), pad(pts.normal, np.float32, 3),
+                pad(pts.dmax, np.float32, 1), pad(pts.dmin, np.float32, 1), pad(pts.desc, np.uint8, 32)]
+        m = MapPointsStruct()
+        m.n = self.n
+        m.state, m.pos, m.normal, m.dmax, m.dmin, m.desc = (a.ctypes.data for a in keep)
+        h = C.c_void_p()
+        _check(load_library().rsc_mpview_create(ctx.h, C.byref(m), C.byref(h)), "rsc_mpview_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().rsc_mpview_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def search_by_projection_kf_many(ctx: Context, kfs, points, Scw, already, occupied, th: int = 10):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cpp:241-352) for each
+    (KFView, MPView, Scw [4,4], already uint8 [points n], occupied uint8 [kf n]) in one launch.  Returns
+    (list of out int32 [kf n] = index into the points of the MapPoint written to vpMatched[idx] or -1,
+    nmatches int32[count], rounds int32[count])."""
+    c = len(kfs)
+    S = np.ascontiguousarray(np.asarray(Scw, np.float32).reshape(c, 16)) if c else np.zeros((1, 16), np.float32)
+    al = [np.ascontiguousarray(a, np.uint8) if p.n else np.zeros(1, np.uint8) for a, p in zip(already, points)]
+    oc = [np.ascontiguousarray(a, np.uint8) if k.n else np.zeros(1, np.uint8) for a, k in zip(occupied, kfs)]
+    out = [np.full(max(k.n, 1), -7, np.int32) for k in kfs]
+    nm = np.zeros(max(c, 1), np.int32)
+    rounds = np.zeros(max(c, 1), np.int32)
+    _check(load_library().rsc_search_by_projection_kf_many(ctx.h, _handles(kfs), _handles(points), c, S, _ptrs(al),
+                                                           _ptrs(oc), int(th), _ptrs(out), nm, rounds),
+           "rsc_search_by_projection_kf_many")
+    return [o[:k.n] for o, k in zip(out, kfs)], nm[:c], rounds[:c]
+
+
+def fuse_sim3_many(ctx: Context, kfs, points, Scw, in_kf, th: float):
+    """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cpp:823-946) for each (KFView,
+    Scw [4,4] with linear() = s R, in_kf uint8 [points n]) against one MPView in one launch.  Returns (list of
+    best_idx int32 [points n], nfused int32[count])."""
+    c = len(kfs)
+    S = np.ascontiguousarray(np.asarray(Scw, np.float32).reshape(c, 16)) if c else np.zeros((1, 16), np.float32)
+    ik = [np.ascontiguousarray(a, np.uint8) if points.n else np.zeros(1, np.uint8) for a in in_kf]
+    best = [np.full(max(points.n, 1), -7, np.int32) for _ in kfs]
+    nf = np.zeros(max(c, 1), np.int32)
+    _check(load_library().rsc_fuse_sim3_many(ctx.h, _handles(kfs), c, points.h, S, _ptrs(ik), float(th),
+                                             _ptrs(best), nf), "rsc_fuse_sim3_many")
+    return [b[:points.n] for b in best], nf[:c]
+
+
+def loop_verify_many(ctx: Context, kf_cur, kf_matched, loop_points, S, matches, already):
+    """The closing stage of LoopClosing::ComputeSim3 (LoopClosing.cpp:318-320, :360-370;
+    rsc_loop_verify_many) on the result of the gated loop events: S [count][8] = LoopGateResult.S,
+    matches[c] int32 [kf_cur n] = matches_out of the gate, already[c] uint8 [points n].  Returns
+    (LoopVerifyResult records, list of projected int32 [kf_cur n])."""
+    c = len(kf_cur)
+    Sd = np.ascontiguousarray(np.asarray(S, np.float64).reshape(c, 8)) if c else np.zeros((1, 8), np.float64)
+    mt = [np.ascontiguousarray(a, np.int32) if k.n else np.full(1, -1, np.int32) for a, k in zip(matches, kf_cur)]
+    al = [np.ascontiguousarray(a, np.uint8) if p.n else np.zeros(1, np.uint8) for a, p in zip(already, loop_points)]
+    proj = [np.full(max(k.n, 1), -7, np.int32) for k in kf_cur]
+    res = (LoopVerifyResult * max(c, 1))()
+    _check(load_library().rsc_loop_verify_many(ctx.h, _handles(kf_cur), _handles(kf_matched), _handles(loop_points),
+                                               c, Sd, _ptrs(mt), _ptrs(al), res, _ptrs(proj)),
+           "rsc_loop_verify_many")
+    return [res[k] for k in range(c)], [p[:k.n] for p, k in zip(proj, kf_cur)]
 
 
 def reloc_refine_many(ctx: Context, frames, kfs, fr, frame_mp, found, n_good_in, Tcw_in):
@@ -602,6 +690,16 @@ def load_library(path: str = LIB_PATH):
                                            C.POINTER(RelocRefinedResult), C.POINTER(C.c_void_p)]
     L.rsc_loop_events_gated.argtypes = [C.POINTER(vp), C.POINTER(LoopCandidate), i32p, C.c_int,
                                         C.POINTER(Sim3Result), C.POINTER(LoopGateResult), C.POINTER(C.c_void_p)]
+    L.rsc_mpview_create.argtypes = [vp, C.POINTER(MapPointsStruct), C.POINTER(vp)]
+    L.rsc_mpview_destroy.argtypes = [vp]
+    L.rsc_search_by_projection_kf_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_,
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
+                                                   C.POINTER(C.c_void_p), i32p, i32p]
+    L.rsc_fuse_sim3_many.argtypes = [vp, C.POINTER(vp), C.c_int, vp, f32p_, C.POINTER(C.c_void_p), C.c_float,
+                                     C.POINTER(C.c_void_p), i32p]
+    L.rsc_loop_verify_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, f64p_,
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       C.POINTER(LoopVerifyResult), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 

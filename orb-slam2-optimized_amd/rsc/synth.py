@@ -1018,3 +1018,105 @@ def make_reloc_refine_event(rng: np.random.Generator, n_kf: int, n_frame: int, c
                       R_true=p.Tcw_true[:3, :3], t_true=p.Tcw_true[:3, 3], inlier_true=np.isin(idx, right))
         out.append((kf, matches, sc))
     return p, out
+
+
+# ---- ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) / Fuse inputs ------------------
+@dataclasses.dataclass
+class MapPointList:
+    """A flat list of distinct MapPoints (mvpLoopMapPoints) as the loop matchers read it (rsc_mappoints)."""
+    n: int
+    state: np.ndarray   # uint8 [n] 1 good, 2 isBad()
+    pos: np.ndarray     # float32 [n,3] GetWorldPos()
+    normal: np.ndarray  # float32 [n,3] GetNormal()
+    dmax: np.ndarray    # float32 [n] mfMaxDistance
+    dmin: np.ndarray    # float32 [n] mfMinDistance
+    desc: np.ndarray    # uint8 [n,32] GetDescriptor()
+
+
+@dataclasses.dataclass
+class LoopProjProblem:
+    """One SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) call."""
+    kf: Sim3KF
+    pts: MapPointList
+    Scw: np.ndarray       # float32 [4,4]: unit rotation, translation as toIso(Sim3) leaves it
+    already: np.ndarray   # uint8 [pts.n] the point is in vpMatched on entry
+    occupied: np.ndarray  # uint8 [kf.n] vpMatched[idx] != NULL on entry
+    th: int = 10
+
+
+def make_loop_projection_problem(rng: np.random.Generator, n_kf: int, n_points: int, n_clusters: int = 20,
+                                 cluster_kps: int = 8, cluster_pts: int = 12, occupied_frac: float = 0.1,
+                                 already_frac: float = 0.05, bad_frac: float = 0.03) -> LoopProjProblem:
+    """A KeyFrame (n_kf keypoints) and a MapPoint list (n_points) seen through a pose Scw.  Crowding:
+    n_clusters groups of cluster_kps keypoints sit within a few pixels of one centre with one octave and
+    (almost) one descriptor, and cluster_pts points project onto that centre with (almost) that descriptor,
+    so the members compete for the same keypoints, the greedy order decides who gets which and the late
+    members find every cached candidate taken.  Every other keypoint has one point of its own; the rest of
+    the list is points that match nothing (random descriptors, behind the camera, facing away, bad)."""
+    sf = scale_factors()
+    assert n_kf >= n_clusters * cluster_kps and n_points >= n_clusters * cluster_pts + (n_kf - n_clusters * cluster_kps)
+    R = random_rotation(rng, 0.3)
+    t = rng.normal(0, 0.5, 3)
+    Ow = -R.T @ t
+    kp = np.zeros((n_kf, 2))
+    octave = np.zeros(n_kf, np.int32)
+    desc = rng.integers(0, 256, (n_kf, 32), dtype=np.uint8)
+    Xc, pdesc, plevel = [], [], []
+    k = 0
+    for c in range(n_clusters):
+        centre = np.array([rng.uniform(40, WIDTH - 40), rng.uniform(40, HEIGHT - 40)])
+        o = int(rng.integers(1, N_LEVELS - 1))
+        base = rng.integers(0, 256, (1, 32), dtype=np.uint8)
+        for _ in range(cluster_kps):
+            kp[k] = centre + rng.uniform(-4, 4, 2)
+            octave[k] = o - int(rng.random() < 0.3)
+            desc[k] = _flip(rng, base, 6.0)[0]
+            k += 1
+        z = rng.uniform(3, 9)
+        X0 = np.array([(centre[0] - CX) / FX * z, (centre[1] - CY) / FY * z, z])
+        for _ in range(cluster_pts):
+            Xc.append(X0 + rng.normal(0, 1e-3, 3))
+            pdesc.append(_flip(rng, base, 4.0)[0])
+            plevel.append(o)
+    n_single = n_kf - k
+    for j in range(n_single):
+        kp[k] = [rng.uniform(2, WIDTH - 2), rng.uniform(2, HEIGHT - 2)]
+        o = int(rng.integers(0, N_LEVELS))
+        octave[k] = max(o - int(rng.random() < 0.3), 0)
+        z = rng.uniform(3, 9)
+        uv = kp[k] + rng.normal(0, 1.0, 2)
+        Xc.append(np.array([(uv[0] - CX) / FX * z, (uv[1] - CY) / FY * z, z]))
+        pdesc.append(_flip(rng, desc[k:k + 1], 10.0)[0])
+        plevel.append(o)
+        k += 1
+    while len(Xc) < n_points:  # points that match nothing
+        z = rng.uniform(3, 9) * (-1.0 if rng.random() < 0.15 else 1.0)
+        Xc.append(np.array([rng.uniform(-3, 3), rng.uniform(-2, 2), z]))
+        pdesc.append(rng.integers(0, 256, 32, dtype=np.uint8))
+        plevel.append(int(rng.integers(0, N_LEVELS)))
+    Xc = np.array(Xc)
+    perm = rng.permutation(n_points)
+    Xc, pdesc, plevel = Xc[perm], np.array(pdesc, np.uint8)[perm], np.array(plevel)[perm]
+    P = (Xc - t) @ R                    # world = R^T (Xc - t)
+    PO = P - Ow
+    dist = np.linalg.norm(PO, axis=1)
+    normal = PO / dist[:, None] + rng.normal(0, 0.05, (n_points, 3))
+    away = rng.random(n_points) < 0.05
+    normal[away] *= -1.0
+    dmax = (dist * np.float64(1.2) ** (plevel - 0.5)).astype(np.float32)  # PredictScale gives plevel
+    dmin = (dmax / sf[N_LEVELS - 1]).astype(np.float32)
+    state = np.where(rng.random(n_points) < bad_frac, 2, 1).astype(np.uint8)
+    pts = MapPointList(n_points, state, P.astype(np.float32), normal.astype(np.float32), dmax, dmin, pdesc)
+    kperm = rng.permutation(n_kf)
+    kp = np.clip(kp[kperm], 0, [WIDTH - 1e-3, HEIGHT - 1e-3]).astype(np.float32)
+    octave, desc = octave[kperm], desc[kperm]
+    begin, feat = build_grid(kp)
+    z1, z3 = np.zeros(n_kf, np.float32), np.zeros((n_kf, 3), np.float32)
+    kf = Sim3KF(n_kf, kp, octave, desc, begin, feat, R.astype(np.float32), t.astype(np.float32),
+                np.zeros(n_kf, np.uint8), z3, z1, z1.copy(), np.zeros((n_kf, 32), np.uint8),
+                np.full(n_kf, -1, np.int64))
+    Scw = np.eye(4)
+    Scw[:3, :3], Scw[:3, 3] = R, t
+    occupied = (rng.random(n_kf) < occupied_frac).astype(np.uint8)
+    already = (rng.random(n_points) < already_frac).astype(np.uint8)
+    return LoopProjProblem(kf, pts, Scw.astype(np.float32), already, occupied)
