@@ -10,7 +10,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fa
 HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
-     facade_loopproj_test chase_mirror_test
+     facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu
 
 $(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
@@ -48,11 +48,15 @@ $(LIBDIR)/kfdb.o: $(CSRC)/kfdb.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/bowvoc.o: $(CSRC)/bowvoc.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/rsc_api.o: $(CSRC)/rsc_api.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 # TEST-ONLY variant: the split eigen stage's hand-off waits give up after one poll, so the fault path
@@ -61,7 +65,7 @@ $(LIBDIR)/kernels_spin1.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DRSC_SPLIT_SPIN_LIMIT=1 -c $< -o $@
 
-$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 facade_test: $(LIBDIR)/facade_test
@@ -78,6 +82,11 @@ facade_loopproj_test: $(LIBDIR)/facade_loopproj_test
 
 $(LIBDIR)/facade_loopproj_test: tests/cpp/facade_loopproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
 	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_loopproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+
+facade_voc_test: $(LIBDIR)/facade_voc_test
+
+$(LIBDIR)/facade_voc_test: tests/cpp/facade_voc_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
+	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_voc_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
 
 # TEST-ONLY host programs: tridiag_qr with and without the mirror() / any_lane() hooks of its
 # rotation sink (tests/test_cpu_chase_mirror.py); the second build runs under the host sanitizers
@@ -105,8 +114,11 @@ frameproj_emu:
 kfproj_emu:
 	$(MAKE) -s -C tests/kfproj_emu
 
-clean:
-	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build
+bowvoc_emu:
+	$(MAKE) -s -C tests/bowvoc_emu
 
-.PHONY: all oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test facade_loopproj_test \
-        chase_mirror_test clean
+clean:
+	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build
+
+.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu facade_test facade_proj_test facade_loopproj_test \
+        facade_voc_test chase_mirror_test clean

@@ -702,6 +702,72 @@ int rsc_kfdb_detect_loop(rsc_kfdb* db, uint64_t kf_id, int n_words, const uint32
  * mnRelocWords}, s[2] = {mLoopScore, mRelocScore}. */
 int rsc_kfdb_state(rsc_kfdb* db, int kf, uint64_t* q, int32_t* w, float* s);
 
+/* ---- ORBVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1194) -------
+ * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cpp:462-469, src/KeyFrame.cpp:46-55): the
+ * descriptors of a view descend the vocabulary tree; the leaves give the BowVector (TF-IDF weights,
+ * L1-normalised), the nodes `levelsup` levels above the leaves give the FeatureVector.  The tree is
+ * uploaded once and stays resident.  Integer descent + the reference's order of FP64 adds: results
+ * are bit-exact with the reference. */
+#define RSC_VOC_TF_IDF 0   /* DBoW2::WeightingType */
+#define RSC_VOC_L1_NORM 0  /* DBoW2::ScoringType */
+typedef struct {
+    int32_t k, L;              /* m_k, m_L of the header line (k is informative: child counts come from parent[]) */
+    int32_t scoring;           /* only RSC_VOC_L1_NORM, */
+    int32_t weighting;         /* with RSC_VOC_TF_IDF (what ORBvoc.txt declares): else RSC_ERR_UNSUPPORTED */
+    int32_t n_nodes;           /* m_nodes.size(), root (node 0) included; >= 2 */
+    const int32_t* parent;     /* [n_nodes] parent[0] ignored; 0 <= parent[i] < i (RSC_ERR_ARG otherwise); the
+                                  children of a node are its children vector in ascending node id; more
+                                  than 32 under one node is RSC_ERR_UNSUPPORTED */
+    const uint8_t* is_leaf;    /* [n_nodes] nIsLeaf > 0: the node is a word (word id = its rank among these) */
+    const uint8_t* desc;       /* [n_nodes][32] node descriptors (the root's is unused) */
+    const double* weight;      /* [n_nodes] node weights (a leaf's weight <= 0: a stopped word) */
+    int32_t lds_budget_bytes;  /* 0 = default.  TEST HOOK: the byte budget (<= 48 KiB) of the tree levels
+                                  staged in LDS by the descent (40 B per node, whole levels) */
+} rsc_vocabulary_nodes;
+
+typedef struct rsc_voc rsc_voc;
+
+int rsc_voc_create(rsc_context* ctx, const rsc_vocabulary_nodes* nodes, rsc_voc** out);
+void rsc_voc_destroy(rsc_voc* voc);
+/* voc->size(): the number of words (rsc_kfdb_create's vocab_words). */
+int rsc_voc_size(const rsc_voc* voc, uint32_t* n_words);
+/* Layout facts (diagnostic): info[0] nodes staged in LDS, [1] the tree levels they make, [2] the
+ * shallowest and [3] the deepest leaf depth, [4] the most children of one node. */
+int rsc_voc_info(const rsc_voc* voc, int32_t* info);
+
+/* One view's transform outputs; every array has room for the view's n entries (node_begin: n + 1)
+ * and may be NULL when not wanted. */
+typedef struct {
+    int32_t n_words;            /* BowVector: size, */
+    uint32_t* word_id;          /*   keys ascending, */
+    double* word_value;         /*   values */
+    int32_t n_nodes;            /* FeatureVector: size, keys ascending, CSR as in rsc_bow_features */
+    uint32_t* node_id;
+    int32_t* node_begin;
+    uint32_t* feat;
+    uint32_t* feature_word;     /* parity hook, per feature: word id, */
+    uint32_t* feature_node;     /*   node id at nid_level, */
+    uint8_t* feature_stopped;   /*   1 when the leaf weight is not > 0 */
+} rsc_voc_output;
+
+/* transform(desc[c], BowVector, FeatureVector, levelsup) for c < count in one call (a Frame and the
+ * KeyFrames inserted since; a batch of relocalization events).  n[c] <= 8192 descriptors of 32
+ * bytes; n[c] = 0 gives empty vectors.  L - levelsup above the vocabulary's shallowest leaf depth is
+ * RSC_ERR_UNSUPPORTED (the reference reads an uninitialised NodeId there).  The work buffers belong to
+ * the vocabulary: calls on one rsc_voc must not overlap (the facade serialises them). */
+int rsc_voc_transform_many(rsc_voc* voc, int count, const int32_t* n, const uint8_t* const* desc, int levelsup,
+                           rsc_voc_output* out);
+/* Device time (ms) of the last transform's descent and build kernels (needs
+ * rsc_context_enable_timing). */
+int rsc_voc_last_kernel_timing(rsc_voc* voc, double* ms2);
+
+/* rsc_bow_create with the FeatureVector computed by the vocabulary: features->n_nodes / node_id /
+ * node_begin / feat are ignored; the view's node arrays are written on the device by the transform.
+ * bow (may be NULL) receives the BowVector (and whatever else it asks for), for rsc_kfdb_add and
+ * rsc_kfdb_detect_*. */
+int rsc_bow_create_transformed(rsc_context* ctx, rsc_voc* voc, const rsc_bow_features* features, int levelsup,
+                               rsc_bow** out, rsc_voc_output* bow);
+
 /* Diagnostics below: `cap` = number of uint64 slots at `out`; RSC_ERR_ARG when it is smaller than
  * the layout (64*24, 64*8, 4096*4 and at most 64*96 words).
  * Diagnostic: wall-clock (100 MHz) phase stamps of the last PnP refine launch, [job < 64][24]:

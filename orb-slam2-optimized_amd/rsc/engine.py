@@ -57,6 +57,8 @@ EXPORTED = [
     "rsc_reloc_refine_many", "rsc_reloc_events_refined",
     "rsc_mpview_create", "rsc_mpview_destroy", "rsc_search_by_projection_kf_many", "rsc_fuse_sim3_many",
     "rsc_loop_verify_many",
+    "rsc_voc_create", "rsc_voc_destroy", "rsc_voc_size", "rsc_voc_info", "rsc_voc_transform_many",
+    "rsc_voc_last_kernel_timing", "rsc_bow_create_transformed",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -158,6 +160,18 @@ class Sim3OptResult(C.Structure):
 class BowFeatures(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc", C.c_void_p), ("angle", C.c_void_p), ("valid", C.c_void_p),
                 ("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("node_begin", C.c_void_p), ("feat", C.c_void_p)]
+
+
+class VocabularyNodes(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32),
+                ("n_nodes", C.c_int32), ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("desc", C.c_void_p),
+                ("weight", C.c_void_p), ("lds_budget_bytes", C.c_int32)]
+
+
+class VocOutput(C.Structure):
+    _fields_ = [("n_words", C.c_int32), ("word_id", C.c_void_p), ("word_value", C.c_void_p),
+                ("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("node_begin", C.c_void_p), ("feat", C.c_void_p),
+                ("feature_word", C.c_void_p), ("feature_node", C.c_void_p), ("feature_stopped", C.c_void_p)]
 
 
 class Sim3KFStruct(C.Structure):
@@ -700,6 +714,15 @@ def load_library(path: str = LIB_PATH):
     L.rsc_loop_verify_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, f64p_,
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                        C.POINTER(LoopVerifyResult), C.POINTER(C.c_void_p)]
+    L.rsc_voc_create.argtypes = [vp, C.POINTER(VocabularyNodes), C.POINTER(vp)]
+    L.rsc_voc_destroy.argtypes = [vp]
+    L.rsc_voc_destroy.restype = None
+    L.rsc_voc_size.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.rsc_voc_info.argtypes = [vp, i32p]
+    L.rsc_voc_transform_many.argtypes = [vp, C.c_int, i32p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(VocOutput)]
+    L.rsc_voc_last_kernel_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rsc_bow_create_transformed.argtypes = [vp, vp, C.POINTER(BowFeatures), C.c_int, C.POINTER(vp),
+                                             C.POINTER(VocOutput)]
     _lib = L
     return L
 
@@ -1453,6 +1476,32 @@ class BowView:
         _check(load_library().rsc_bow_create(ctx.h, C.byref(f), C.byref(h)), "rsc_bow_create")
         self.h = h
 
+    @classmethod
+    def from_descriptors(cls, ctx: Context, voc, desc, angle, valid=None, levelsup: int = 4):
+        """A BowView whose FeatureVector the vocabulary computes on the device
+        (rsc_bow_create_transformed).  The view's BowVector is left in .word_id / .word_value (for
+        KeyFrameDatabase.add / detect_*)."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        self.n = len(d)
+        a = np.ascontiguousarray(angle, np.float32)
+        v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+        f = BowFeatures()
+        f.n = self.n
+        f.desc, f.angle = d.ctypes.data, a.ctypes.data
+        f.valid = None if v is None else v.ctypes.data
+        buf = _VocBuffers(self.n, per_feature=False, feature_vector=False)
+        o = VocOutput()
+        buf.fill(o)
+        h = C.c_void_p()
+        _check(load_library().rsc_bow_create_transformed(ctx.h, voc.h, C.byref(f), int(levelsup), C.byref(h), C.byref(o)),
+               "rsc_bow_create_transformed")
+        self.h = h
+        r = buf.result(o)
+        self.word_id, self.word_value = r["word_id"], r["word_value"]
+        return self
+
     def set_valid(self, valid):
         _check(load_library().rsc_bow_set_valid(self.h, np.ascontiguousarray(valid, np.uint8)), "rsc_bow_set_valid")
 
@@ -1509,3 +1558,96 @@ def search_by_bow_kf_many(ctx: Context, kf1, kf2s, nnratio=0.75, check_orientati
     (LoopClosing::ComputeSim3, LoopClosing.cpp:238-251).  Returns (matches12 int32[count, kf1.n],
     nmatches int32[count])."""
     return BowSearch(ctx, kf1, kf2s, False, nnratio, check_orientation).run()
+
+
+class _VocBuffers:
+    """Host arrays behind one rsc_voc_output (room for n entries each)."""
+
+    def __init__(self, n: int, per_feature: bool = True, feature_vector: bool = True):
+        m = max(int(n), 1)
+        self.n = int(n)
+        self.word_id, self.word_value = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+        self.node_id, self.node_begin = np.zeros(m, np.uint32), np.zeros(m + 1, np.int32)
+        self.feat = np.zeros(m, np.uint32)
+        self.f_word, self.f_node, self.f_stopped = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        self.per_feature, self.feature_vector = per_feature, feature_vector
+
+    def fill(self, o: VocOutput):
+        o.word_id, o.word_value = self.word_id.ctypes.data, self.word_value.ctypes.data
+        if self.feature_vector:
+            o.node_id, o.node_begin, o.feat = self.node_id.ctypes.data, self.node_begin.ctypes.data, self.feat.ctypes.data
+        if self.per_feature:
+            o.feature_word, o.feature_node = self.f_word.ctypes.data, self.f_node.ctypes.data
+            o.feature_stopped = self.f_stopped.ctypes.data
+
+    def result(self, o: VocOutput) -> dict:
+        nw, nn = int(o.n_words), int(o.n_nodes)
+        r = dict(word_id=self.word_id[:nw].copy(), word_value=self.word_value[:nw].copy())
+        if self.feature_vector:
+            begin = self.node_begin[:nn + 1].copy()
+            r.update(node_id=self.node_id[:nn].copy(), node_begin=begin, feat=self.feat[:int(begin[nn])].copy())
+        if self.per_feature:
+            r.update(f_word=self.f_word[:self.n].copy(), f_node=self.f_node[:self.n].copy(),
+                     f_stopped=self.f_stopped[:self.n].copy())
+        return r
+
+
+class Vocabulary:
+    """The ORB vocabulary resident in HBM (rsc_voc_*): DBoW2 TemplatedVocabulary::transform, i.e.
+    Frame::ComputeBoW / KeyFrame::ComputeBoW, on the device.  `nodes` is an object with k, L, scoring,
+    weighting, parent int32[], is_leaf uint8[], desc uint8[,32], weight float64[] (rsc.synth.Vocabulary).
+    lds_budget_bytes: test hook of the LDS staging cut (0 = default)."""
+
+    def __init__(self, ctx: Context, nodes, lds_budget_bytes: int = 0):
+        self.ctx = ctx
+        arrs = [np.ascontiguousarray(nodes.parent, np.int32), np.ascontiguousarray(nodes.is_leaf, np.uint8),
+                np.ascontiguousarray(nodes.desc, np.uint8).reshape(-1), np.ascontiguousarray(nodes.weight, np.float64)]
+        v = VocabularyNodes()
+        v.k, v.L, v.scoring, v.weighting = int(nodes.k), int(nodes.L), int(nodes.scoring), int(nodes.weighting)
+        v.n_nodes = len(arrs[0])
+        v.parent, v.is_leaf, v.desc, v.weight = (a.ctypes.data for a in arrs)
+        v.lds_budget_bytes = int(lds_budget_bytes)
+        h = C.c_void_p()
+        _check(load_library().rsc_voc_create(ctx.h, C.byref(v), C.byref(h)), "rsc_voc_create")
+        self.h = h
+        n = C.c_uint32()
+        _check(load_library().rsc_voc_size(self.h, C.byref(n)), "rsc_voc_size")
+        self.size = int(n.value)
+
+    def info(self) -> dict:
+        a = np.zeros(8, np.int32)
+        _check(load_library().rsc_voc_info(self.h, a), "rsc_voc_info")
+        return dict(lds_nodes=int(a[0]), lds_levels=int(a[1]), min_leaf_depth=int(a[2]), max_depth=int(a[3]),
+                    max_children=int(a[4]))
+
+    def transform_many(self, descs, levelsup: int = 4, per_feature: bool = True):
+        """transform() of every view of `descs` (uint8 [n,32] each) in one call -> a list of dicts:
+        word_id uint32[], word_value float64[] (BowVector), node_id uint32[], node_begin int32[],
+        feat uint32[] (FeatureVector as CSR) and, with per_feature, f_word / f_node / f_stopped [n]."""
+        ds = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descs]
+        c = len(ds)
+        n = np.array([len(d) for d in ds] + [0], np.int32)
+        ptrs = (C.c_void_p * max(c, 1))(*[d.ctypes.data for d in ds])
+        outs = (VocOutput * max(c, 1))()
+        bufs = [_VocBuffers(len(d), per_feature) for d in ds]
+        for b, o in zip(bufs, outs):
+            b.fill(o)
+        _check(load_library().rsc_voc_transform_many(self.h, c, n, ptrs, int(levelsup), outs), "rsc_voc_transform_many")
+        return [b.result(o) for b, o in zip(bufs, outs)]
+
+    def transform(self, desc, levelsup: int = 4) -> dict:
+        return self.transform_many([desc], levelsup)[0]
+
+    def last_kernel_timing(self):
+        """(descent, build) device milliseconds of the last transform (Context.enable_timing)."""
+        ms = (C.c_double * 2)()
+        _check(load_library().rsc_voc_last_kernel_timing(self.h, ms), "rsc_voc_last_kernel_timing")
+        return float(ms[0]), float(ms[1])
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().rsc_voc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()

@@ -1120,3 +1120,97 @@ def make_loop_projection_problem(rng: np.random.Generator, n_kf: int, n_points: 
     occupied = (rng.random(n_kf) < occupied_frac).astype(np.uint8)
     already = (rng.random(n_points) < already_frac).astype(np.uint8)
     return LoopProjProblem(kf, pts, Scw.astype(np.float32), already, occupied)
+
+
+# ---- ORBVocabulary (DBoW2 TemplatedVocabulary) --------------------------------------------------
+@dataclasses.dataclass
+class Vocabulary:
+    """A DBoW2 vocabulary tree as ORBvoc.txt lists it (rsc_vocabulary_nodes): node 0 is the root,
+    parent[i] < i, the children of a node are its nodes in ascending id."""
+    k: int
+    L: int
+    scoring: int            # 0 = L1_NORM
+    weighting: int          # 0 = TF_IDF
+    parent: np.ndarray      # int32 [nodes]
+    is_leaf: np.ndarray     # uint8 [nodes] nIsLeaf: the node is a word
+    desc: np.ndarray        # uint8 [nodes,32]
+    weight: np.ndarray      # float64 [nodes]
+
+    @property
+    def n_nodes(self) -> int:
+        return len(self.parent)
+
+
+def make_vocabulary(rng: np.random.Generator, k: int, L: int, child_counts=None, leaf_prob: float = 0.0,
+                    min_leaf_depth: int | None = None, zero_weight_frac: float = 0.0, duplicate_frac: float = 0.0,
+                    nonword_leaf_frac: float = 0.0, density: int = 3) -> Vocabulary:
+    """A hierarchical vocabulary of depth L, numbered level by level.  A child's descriptor is its
+    parent's with random bit flips (each bit with probability 2^-density), so a descriptor near a
+    leaf descends to it.  child_counts: the inner nodes take their child counts from this sequence
+    in turn instead of k (irregular trees).  leaf_prob / min_leaf_depth: a node at depth >=
+    min_leaf_depth (default L) below L stays childless with this probability (leaves at several
+    depths).  zero_weight_frac: leaves with weight 0 (stopped words).  duplicate_frac: a child
+    copies the descriptor of its preceding sibling (distance ties).  nonword_leaf_frac: childless
+    nodes with nIsLeaf = 0 that keep a positive weight."""
+    min_leaf_depth = L if min_leaf_depth is None else int(min_leaf_depth)
+    counts_seq = None if child_counts is None else np.asarray(child_counts, np.int64)
+    parent = [np.zeros(1, np.int32)]
+    desc = [rng.integers(0, 256, size=(1, 32), dtype=np.uint8)]
+    childless = [np.zeros(1, bool)]
+    level_ids = np.zeros(1, np.int64)
+    n, drawn = 1, 0
+    for d in range(1, L + 1):
+        inner = level_ids[~childless[-1][-len(level_ids):]] if len(level_ids) else level_ids
+        if len(inner) == 0:
+            break
+        if counts_seq is None:
+            cnt = np.full(len(inner), k, np.int64)
+        else:
+            cnt = counts_seq[(drawn + np.arange(len(inner))) % len(counts_seq)]
+            drawn += len(inner)
+        par = np.repeat(inner, cnt)
+        m = len(par)
+        pdesc = np.concatenate(desc)[par]
+        mask = rng.integers(0, 256, size=(m, 32), dtype=np.uint8)
+        for _ in range(density - 1):
+            mask &= rng.integers(0, 256, size=(m, 32), dtype=np.uint8)
+        cdesc = pdesc ^ mask
+        if duplicate_frac > 0:
+            dup = np.flatnonzero((rng.random(m) < duplicate_frac) & (np.arange(m) > 0))
+            for j in dup:
+                if par[j] == par[j - 1]:
+                    cdesc[j] = cdesc[j - 1]
+        stop = np.ones(m, bool) if d == L else (rng.random(m) < leaf_prob) & (d >= min_leaf_depth)
+        parent.append(par.astype(np.int32))
+        desc.append(cdesc)
+        childless.append(stop)
+        level_ids = np.arange(n, n + m, dtype=np.int64)
+        n += m
+    parent = np.concatenate(parent)
+    desc = np.concatenate(desc)
+    leaf = np.concatenate(childless)
+    leaf[0] = False
+    weight = np.zeros(n, np.float64)
+    weight[leaf] = rng.uniform(0.5, 10.0, int(leaf.sum()))
+    weight[leaf & (rng.random(n) < zero_weight_frac)] = 0.0
+    is_leaf = leaf.astype(np.uint8)
+    is_leaf[leaf & (rng.random(n) < nonword_leaf_frac)] = 0
+    return Vocabulary(int(k), int(L), 0, 0, parent, is_leaf, np.ascontiguousarray(desc), weight)
+
+
+def sample_descriptors(rng: np.random.Generator, voc: Vocabulary, n: int, mean_flips: float = 6.0,
+                       random_frac: float = 0.1) -> np.ndarray:
+    """n ORB descriptors for a vocabulary: copies of random childless nodes' descriptors with
+    Poisson(mean_flips) bit flips, and a fraction of uniform random ones."""
+    has_child = np.zeros(voc.n_nodes, bool)
+    has_child[voc.parent[1:]] = True
+    leaves = np.flatnonzero(~has_child)
+    out = voc.desc[rng.choice(leaves, size=n)].copy()
+    flips = np.minimum(rng.poisson(mean_flips, n), 255)
+    for j in range(int(flips.max()) if n else 0):
+        rows = np.flatnonzero(flips > j)
+        bits = rng.integers(0, 256, len(rows))
+        out[rows, bits // 8] ^= (1 << (bits % 8)).astype(np.uint8)
+    rnd = rng.random(n) < random_frac
+    out[rnd] = rng.integers(0, 256, size=(int(rnd.sum()), 32), dtype=np.uint8)
+    return np.ascontiguousarray(out)

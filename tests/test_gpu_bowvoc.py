@@ -1,0 +1,317 @@
+"""GPU parity of the vocabulary transform (Frame::ComputeBoW / KeyFrame::ComputeBoW: DBoW2
+TemplatedVocabulary::transform, TemplatedVocabulary.h:1127-1194) through the C ABI (rsc_voc_*,
+rsc_bow_create_transformed) against the sequential restatement tests/bowvoc_ref.py: BowVector,
+FeatureVector and the per-feature (word, node, stopped) triples bit for bit (doubles as uint64), no
+tolerance; then the transformed vectors feeding SearchByBoW and the KeyFrameDatabase."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bowvoc_cases as bc
+from bowvoc_ref import RefVocabulary, assert_same
+from gpu_common import ctx
+from rsc import engine, synth
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+_cache = {}
+
+
+def pair(name, make, **kw):
+    """(device vocabulary, restatement, nodes) of a named case, built once."""
+    if name not in _cache:
+        voc = make()
+        _cache[name] = (engine.Vocabulary(ctx(), voc, **kw), RefVocabulary(voc), voc)
+    return _cache[name]
+
+
+def basic():
+    return pair("basic", lambda: synth.make_vocabulary(np.random.default_rng(11), 3, 2, zero_weight_frac=0.2))
+
+
+def mid():
+    return pair("mid", lambda: synth.make_vocabulary(np.random.default_rng(12), 10, 3, zero_weight_frac=0.05))
+
+
+def check(g, r, desc, levelsup):
+    got = g.transform(desc, levelsup)
+    ref = r.transform(desc, levelsup)
+    assert_same(got, ref, (len(desc), levelsup))
+    return got, ref
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65])
+def test_basic_sizes(n):
+    g, r, voc = basic()
+    assert g.size == r.size() == 9
+    desc = synth.sample_descriptors(np.random.default_rng(100 + n), voc, n, mean_flips=20.0)
+    for levelsup in (0, 1, 2, 5):  # nid_level 2, 1, 0 (root) and below 0
+        got, _ = check(g, r, desc, levelsup)
+    if n == 0:
+        assert len(got["word_id"]) == 0 and len(got["node_id"]) == 0 and list(got["node_begin"]) == [0]
+
+
+def test_mid_size():
+    g, r, voc = mid()
+    desc = synth.sample_descriptors(np.random.default_rng(120), voc, 257, mean_flips=12.0)
+    got, _ = check(g, r, desc, 1)
+    assert len(got["word_id"]) > 100 and len(got["node_id"]) > 20
+
+
+def test_deep_tree_lds_cut():
+    """k = 4, L = 6 (5461 nodes): the same transform with the staging cut after the root, after level
+    2 and at the default budget (after level 4) — staged levels, gathered levels and runs of children
+    on either side of the cut."""
+    voc = synth.make_vocabulary(np.random.default_rng(13), 4, 6, zero_weight_frac=0.05)
+    assert voc.n_nodes == 5461
+    r = RefVocabulary(voc)
+    desc = synth.sample_descriptors(np.random.default_rng(130), voc, 300, mean_flips=8.0)
+    ref = r.transform(desc, 4)
+    for budget, nodes, levels in ((40, 1, 1), (1000, 21, 3), (0, 341, 5)):
+        g = engine.Vocabulary(ctx(), voc, lds_budget_bytes=budget)
+        info = g.info()
+        assert (info["lds_nodes"], info["lds_levels"]) == (nodes, levels), info
+        assert (info["min_leaf_depth"], info["max_depth"], info["max_children"]) == (6, 6, 4)
+        assert_same(g.transform(desc, 4), ref, budget)
+        g.close()
+
+
+def irregular():
+    return pair("irregular", bc.irregular_vocabulary)
+
+
+def test_irregular_tree():
+    g, r, voc = irregular()
+    nch = np.bincount(voc.parent[1:], minlength=voc.n_nodes)
+    assert {1, 2, 16, 17, 32} <= set(nch.tolist())
+    leaf_depths = set(bc.depths(voc)[nch == 0].tolist())
+    assert leaf_depths == {2, 3, 4, 5}, leaf_depths
+    info = g.info()
+    assert (info["min_leaf_depth"], info["max_depth"], info["max_children"]) == (2, 5, 32)
+    desc = synth.sample_descriptors(np.random.default_rng(140), voc, 400, mean_flips=10.0)
+    got, ref = check(g, r, desc, 3)  # nid_level = 5 - 3 = 2
+    leaf_of = {int(w): 0 for w in got["f_word"]}
+    assert len(leaf_of) > 50
+    check(g, r, desc[:70], 7)
+
+
+def test_unsupported_nid_level():
+    g, r, voc = irregular()
+    desc = synth.sample_descriptors(np.random.default_rng(141), voc, 10)
+    with pytest.raises(RuntimeError, match=r"\(-4\)"):
+        g.transform(desc, 2)  # nid_level 3 > the shallowest leaf depth 2
+
+
+def test_loader_quirk_shape():
+    """A root with one extra zero-weight childless child (the reference loader's trailing-newline
+    node): the features that choose it appear in neither vector."""
+    base = synth.make_vocabulary(np.random.default_rng(15), 3, 2)
+    voc, extra = bc.with_loader_quirk(base)
+    g, r = engine.Vocabulary(ctx(), voc), RefVocabulary(voc)
+    assert g.size == r.size() == 9
+    rng = np.random.default_rng(150)
+    desc = synth.sample_descriptors(rng, base, 90, mean_flips=5.0, random_frac=0.0)
+    hit = np.arange(0, 90, 3)
+    desc[hit] = extra
+    desc[hit[::2], 0] ^= 1  # some one bit away
+    got, ref = check(g, r, desc, 1)
+    assert ref["f_stopped"][hit].all() and (ref["f_node"][hit] == voc.n_nodes - 1).all()
+    assert not np.isin(hit, got["feat"]).any() and len(got["feat"]) == 60
+    assert voc.n_nodes - 1 not in got["node_id"]
+
+
+def test_ties_go_to_the_first_child():
+    voc = synth.make_vocabulary(np.random.default_rng(16), 4, 3, duplicate_frac=0.5)
+    g, r = engine.Vocabulary(ctx(), voc), RefVocabulary(voc)
+    nch = np.bincount(voc.parent[1:], minlength=voc.n_nodes)
+    leaves = np.flatnonzero(nch == 0)
+    desc = voc.desc[leaves].copy()  # exact copies: duplicated siblings tie at every level they occur
+    got, ref = check(g, r, desc, 1)
+    dup = [i for i in leaves if i > 1 and voc.parent[i] == voc.parent[i - 1] and (voc.desc[i] == voc.desc[i - 1]).all()]
+    assert len(dup) >= 10
+    words = np.cumsum(voc.is_leaf[1:] > 0) - 1  # word id of node i at [i - 1]
+    for i in dup:  # a duplicate's own descriptor lands on an earlier sibling
+        assert got["f_word"][list(leaves).index(i)] < words[i - 1]
+
+
+@pytest.mark.parametrize("w", [0.1, float(np.log(10 / 3)), float(np.log(1000 / 7))])
+def test_ordered_word_sum(w):
+    """40 identical descriptors: the word's value is 40 sequential adds (not 40 * w), visible through
+    the L1 normalisation against a second word."""
+    g0, r0, voc0 = basic()
+    import copy
+    voc = copy.deepcopy(voc0)
+    voc.weight[voc.weight > 0] = w
+    voc.weight[-1] = 0.7
+    g, r = engine.Vocabulary(ctx(), voc), RefVocabulary(voc)
+    live = np.flatnonzero(voc.weight > 0)
+    desc = np.concatenate([np.repeat(voc.desc[live[0]][None], 40, 0), np.repeat(voc.desc[-1][None], 3, 0)])
+    got, ref = check(g, r, desc, 1)
+    assert len(ref["word_id"]) == 2
+    s = 0.0
+    for _ in range(40):
+        s += w
+    t = 0.7 + 0.7 + 0.7
+    assert ref["word_value"][0] == s / (s + t)
+    if w == 0.1:  # here the product form differs from the sequential sum, before and after the division
+        assert s != 40 * w and ref["word_value"][0] != (40 * w) / (40 * w + t)
+
+
+def test_all_words_stopped():
+    import copy
+    _, _, voc0 = basic()
+    voc = copy.deepcopy(voc0)
+    voc.weight[:] = 0.0
+    g, r = engine.Vocabulary(ctx(), voc), RefVocabulary(voc)
+    desc = synth.sample_descriptors(np.random.default_rng(170), voc, 50)
+    got, ref = check(g, r, desc, 1)
+    assert len(got["word_id"]) == 0 and len(got["node_id"]) == 0 and len(got["feat"]) == 0
+    assert ref["norm"] == 0.0 and got["f_stopped"].all()
+
+
+def test_batch_of_views():
+    g, r, voc = mid()
+    rng = np.random.default_rng(180)
+    descs = [synth.sample_descriptors(rng, voc, n, mean_flips=12.0) for n in (0, 1, 700, 64)]
+    got = g.transform_many(descs, 1)
+    assert len(got) == 4
+    for d, x in zip(descs, got):
+        assert_same(x, r.transform(d, 1), len(d))
+
+
+def test_largest_view():
+    g, r, voc = basic()
+    desc = synth.sample_descriptors(np.random.default_rng(190), voc, 8192, mean_flips=30.0)
+    got, _ = check(g, r, desc, 1)
+    assert len(got["feat"]) + int(got["f_stopped"].sum()) == 8192
+
+
+def _raw_create(voc, **over):
+    L = engine.load_library()
+    arrs = [np.ascontiguousarray(voc.parent, np.int32), np.ascontiguousarray(voc.is_leaf, np.uint8),
+            np.ascontiguousarray(voc.desc, np.uint8), np.ascontiguousarray(voc.weight, np.float64)]
+    v = engine.VocabularyNodes()
+    v.k, v.L, v.scoring, v.weighting, v.n_nodes = voc.k, voc.L, voc.scoring, voc.weighting, voc.n_nodes
+    v.parent, v.is_leaf, v.desc, v.weight = (a.ctypes.data for a in arrs)
+    for k, x in over.items():
+        setattr(v, k, x)
+    h = C.c_void_p()
+    st = L.rsc_voc_create(ctx().h, C.byref(v), C.byref(h))
+    if st == 0:
+        L.rsc_voc_destroy(h)
+    return st
+
+
+def test_bad_arguments():
+    import copy
+    g, _, voc = basic()
+    assert _raw_create(voc) == 0
+    bad = copy.deepcopy(voc)
+    bad.parent[5] = 5
+    assert _raw_create(bad) == -1  # RSC_ERR_ARG: the reference would index m_nodes out of bounds
+    bad.parent[5] = 9
+    assert _raw_create(bad) == -1
+    wide = synth.make_vocabulary(np.random.default_rng(19), 33, 1)
+    assert _raw_create(wide) == -4  # RSC_ERR_UNSUPPORTED: 33 children
+    assert _raw_create(synth.make_vocabulary(np.random.default_rng(19), 32, 1)) == 0
+    assert _raw_create(voc, scoring=1) == -4
+    assert _raw_create(voc, weighting=1) == -4
+    with pytest.raises(RuntimeError, match=r"\(-4\)"):
+        g.transform(np.zeros((8193, 32), np.uint8), 1)
+
+
+def _views(voc, rng, n_a=500, n_b=450):
+    """Two related views: B copies descriptors of A with a few bit flips and a common rotation."""
+    da = synth.sample_descriptors(rng, voc, n_a, mean_flips=10.0)
+    src = rng.choice(n_a, size=n_b, replace=False)
+    db = synth._flip_bits(rng, da[src], rng.poisson(6, n_b))
+    aa = rng.uniform(0, 360, n_a).astype(np.float32)
+    ab = np.mod(aa[src] + np.float32(30.0), 360).astype(np.float32)
+    va, vb = (rng.random(n_a) < 0.85).astype(np.uint8), (rng.random(n_b) < 0.85).astype(np.uint8)
+    return (da, aa, va), (db, ab, vb)
+
+
+def test_bow_view_from_descriptors_end_to_end():
+    """BowView.from_descriptors against rsc_bow_create on the restatement's FeatureVector: the same
+    SearchByBoW results in both overloads (and after a validity refresh)."""
+    g, r, voc = mid()
+    c = ctx()
+    A, B = _views(voc, np.random.default_rng(200))
+    new, old = [], []
+    for d, a, v in (A, B):
+        new.append(engine.BowView.from_descriptors(c, g, d, a, v, levelsup=1))
+        ref = r.transform(d, 1)
+        old.append(engine.BowView(c, synth.BowFeatures(len(d), d, a, v, ref["node_id"], ref["node_begin"],
+                                                       ref["feat"])))
+        assert np.array_equal(new[-1].word_id, ref["word_id"])
+        assert np.array_equal(new[-1].word_value.view(np.uint64), ref["word_value"].view(np.uint64))
+    for rnd in range(2):
+        mf_n, nf_n = engine.search_by_bow_frame_many(c, [new[0]], new[1])
+        mf_o, nf_o = engine.search_by_bow_frame_many(c, [old[0]], old[1])
+        mk_n, nk_n = engine.search_by_bow_kf_many(c, new[0], [new[1]])
+        mk_o, nk_o = engine.search_by_bow_kf_many(c, old[0], [old[1]])
+        assert np.array_equal(nf_n, nf_o) and np.array_equal(mf_n, mf_o)
+        assert np.array_equal(nk_n, nk_o) and np.array_equal(mk_n, mk_o)
+        assert nf_n[0] > 50 and nk_n[0] > 50, (nf_n, nk_n)
+        valid = (np.random.default_rng(201).random(len(A[0])) < 0.5).astype(np.uint8)
+        new[0].set_valid(valid)
+        old[0].set_valid(valid)
+
+
+def test_database_end_to_end():
+    """A KeyFrameDatabase fed with transformed BowVectors and one fed with the restatement's: the same
+    relocalization candidates."""
+    g, r, voc = mid()
+    c = ctx()
+    rng = np.random.default_rng(210)
+    n_kf = 24
+    base = synth.sample_descriptors(rng, voc, 1500, mean_flips=10.0)
+    descs = [base[(40 * k + np.arange(400)) % 1500] for k in range(n_kf)]  # neighbours overlap
+    bows = g.transform_many(descs, 1, per_feature=False)
+    db_g = engine.KeyFrameDatabase(c, n_kf, vocab_words=g.size)
+    db_r = engine.KeyFrameDatabase(c, n_kf, vocab_words=r.size())
+    for k in range(n_kf):
+        ref = r.transform(descs[k], 1)
+        db_g.add(k, bows[k]["word_id"], bows[k]["word_value"])
+        db_r.add(k, ref["word_id"], ref["word_value"])
+        best = [j for j in (k - 2, k - 1, k + 1, k + 2) if 0 <= j < n_kf]
+        db_g.set_covisibility(k, best)
+        db_r.set_covisibility(k, best)
+    found = 0
+    for q, start in enumerate((0, 330, 700)):
+        qd = synth._flip_bits(rng, base[(start + np.arange(400)) % 1500], rng.poisson(2, 400))
+        qg, qr = g.transform(qd, 1), r.transform(qd, 1)
+        a = db_g.detect_relocalization(1000 + q, qg["word_id"], qg["word_value"])
+        b = db_r.detect_relocalization(1000 + q, qr["word_id"], qr["word_value"])
+        assert list(a) == list(b), (q, a, b)
+        found += len(a)
+    assert found > 0
+
+
+def test_facade_vocabulary_program(tmp_path):
+    """csrc/facade/ORBVocabulary.hpp: the C++ program loads a text vocabulary (with a trailing
+    newline), transforms descriptors on the device into std::map vectors and writes them out
+    (tests/cpp/facade_voc_test.cpp); they equal the restatement's, doubles bit for bit."""
+    exe = os.path.join(ROOT, "orb-slam2-optimized_amd", "lib", "facade_voc_test")
+    assert os.path.exists(exe), "facade_voc_test not built"
+    voc, desc = bc.golden_case()
+    bc.write_text_vocabulary(voc, tmp_path / "voc.txt", trailing_newline=True)
+    desc.tofile(tmp_path / "desc.bin")
+    out = subprocess.run([exe, "device", str(tmp_path / "voc.txt"), str(tmp_path / "desc.bin"), "1",
+                          str(tmp_path / "out.txt")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "facade_voc_test device: ok" in out.stdout, out.stdout + out.stderr
+    r = RefVocabulary(voc)
+    ref = r.transform(desc, 1)
+    lines = open(tmp_path / "out.txt").read().split("\n")
+    assert lines[0] == f"size {r.size()} features {len(desc)}"
+    words = [l.split() for l in lines if l.startswith("W ")]
+    nodes = [l.split() for l in lines if l.startswith("N ")]
+    assert [int(w[1]) for w in words] == ref["word_id"].tolist()
+    assert [int(w[2], 16) for w in words] == ref["word_value"].view(np.uint64).tolist()
+    assert [int(x[1]) for x in nodes] == ref["node_id"].tolist()
+    for j, x in enumerate(nodes):
+        assert [int(v) for v in x[2:]] == ref["feat"][ref["node_begin"][j]:ref["node_begin"][j + 1]].tolist()
