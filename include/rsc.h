@@ -371,7 +371,20 @@ typedef struct {
 } rsc_poseopt_result;
 
 /* Optimizer::PoseOptimization on `count` Frames in one launch (one workgroup per Frame).
- * outlier[c] receives mvbOutlier for the slots with a map point (others untouched); may be NULL. */
+ * outlier[c] receives mvbOutlier for the slots with a map point (others untouched); may be NULL.
+ *
+ * Limits and degenerate inputs.  A Frame may have any number of slots but at most 8192 edges (slots
+ * with a map point): more returns RSC_ERR_UNSUPPORTED before anything runs, and the context stays
+ * usable.  The values are taken as given and treated as the reference's g2o code treats them; nothing
+ * is validated or clamped.  A NaN or infinite Xw, uv or Tcw entry, or a point with z == 0 in the camera
+ * frame, makes activeRobustChi2 non-finite: rho is NaN, no trial is accepted, every round runs its 10
+ * iterations of one trial, the pose returned is the (normalised) entry pose — NaN where Tcw was NaN —
+ * and such an edge is never an outlier (NaN > 5.991 is false).  inv_sigma2 == 0, or fx == fy == 0 on a
+ * monocular Frame, gives H == 0 and rho == 0: every optimize() call ends after one trial.  A negative inv_sigma2 (ORB-SLAM2
+ * never produces one) makes the LDLT of H + lambda I non-positive: the previous update _x is applied
+ * again and tempChi becomes DBL_MAX, as LinearSolverDense and solve() do.  No input makes the call
+ * loop: every loop of the kernel is bounded by the edge count and the 4 x 10 x 10 LM schedule.
+ * tests/test_gpu_lm_edges.py holds these cases against the oracle. */
 int rsc_pose_optimization_many(rsc_context* ctx, const rsc_poseopt_problem* problems, int count,
                                rsc_poseopt_result* out, uint8_t* const* outlier);
 
@@ -408,7 +421,19 @@ typedef struct {
 } rsc_sim3opt_result;
 
 /* OptimizeSim3 on `count` KeyFrame pairs in one launch (one workgroup per pair).  keep[c] (may be
- * NULL) receives per slot 0 where vpMatches1[i] is set to NULL (an outlier), 1 elsewhere. */
+ * NULL) receives per slot 0 where vpMatches1[i] is set to NULL (an outlier), 1 elsewhere.
+ *
+ * Limits and degenerate inputs.  A pair may have any number of slots but at most 8192 valid
+ * correspondences: more returns RSC_ERR_UNSUPPORTED before anything runs, and the context stays
+ * usable; a pair without a valid correspondence returns 0 with S untouched.  The values are taken as
+ * given, as the reference's g2o code treats them.  A NaN or infinite point, observation or S entry, or
+ * s == 0, makes activeRobustChi2 non-finite: rho is NaN, no trial is accepted, both optimize() calls
+ * run all their iterations with one trial each, S is returned as it came and no correspondence is
+ * removed (NaN > th2 is false).  inv1 == inv2 == 0 gives H == 0 and rho == 0: one trial per optimize().
+ * Negative inv1 / inv2 (ORB-SLAM2 never produces them) make the LDLT non-positive: the previous update
+ * is applied again and tempChi becomes DBL_MAX.  Every loop and every hand-off wait of the kernel (both
+ * forms) is bounded independently of the data.  tests/test_gpu_lm_edges.py holds these cases against
+ * the oracle. */
 int rsc_optimize_sim3_many(rsc_context* ctx, const rsc_sim3opt_problem* problems, int count,
                            rsc_sim3opt_result* out, uint8_t* const* keep);
 

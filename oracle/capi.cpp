@@ -584,6 +584,25 @@ int ora_pose_optimization(int n, const uint8_t* has_mp, const float* uv, const f
     return r;
 }
 
+// ora_pose_optimization plus the call's LM branch record (lm_branches.h): branches[11] = trials, !ok2,
+// non-finite tempChi, NaN rho, rejected, ended by qmax == 10 / rho == 0 / nBadLM >= 3, optimize() calls
+// without an active edge, iterations entered with a non-finite currentChi, accepted !ok2 trials.  Same
+// arithmetic and results.
+int ora_pose_optimization_branches(int n, const uint8_t* has_mp, const float* uv, const float* Xw,
+                                   const float* inv_sigma2, float fx, float fy, float cx, float cy,
+                                   const float* Tcw_in, float* Tcw_out, uint8_t* outlier, int32_t* stats,
+                                   const float* u_right, float bf, int32_t* branches) {
+    PoseOptInput in{n, has_mp, uv, Xw, inv_sigma2, fx, fy, cx, cy, {}, u_right, bf};
+    std::memcpy(in.Tcw, Tcw_in, sizeof(in.Tcw));
+    PoseOptStats st{};
+    LmBranches br{};
+    const int r = pose_optimization(in, Tcw_out, outlier, &st, &br);
+    if (stats) { stats[0] = st.rounds; stats[1] = st.lm_iterations; stats[2] = st.lm_trials; }
+    static_assert(kLmBranchFields == 11, "branches[11]");
+    std::memcpy(branches, &br, sizeof(br));
+    return r;
+}
+
 // Batch of problems (bench cpu_baseline): problem c has edges [off[c], off[c+1]) (all with map points).
 void ora_pose_optimization_batch(int count, const int64_t* off, const float* uv, const float* Xw,
                                  const float* inv_sigma2, float fx, float fy, float cx, float cy,
@@ -602,9 +621,9 @@ void ora_pose_optimization_batch(int count, const int64_t* off, const float* uv,
 // ---- Optimizer::OptimizeSim3 (Optimizer.cpp:1054-1250) ----
 // poses[24] = R1w 9, t1w 3, R2w 9, t2w 3; K[8] = K1 (fx, fy, cx, cy), K2; S[8] = q (x, y, z, w), t, s
 // in/out; stats[4] = nCorrespondences, nBad, LM iterations, LM trials.  Returns nIn.
-int ora_optimize_sim3(int n, const uint8_t* valid, const float* X1w, const float* X2w, const float* uv1,
-                      const float* uv2, const float* inv1, const float* inv2, const float* poses, const float* K,
-                      float th2, double* S, uint8_t* keep, int32_t* stats) {
+static int optimize_sim3_c(int n, const uint8_t* valid, const float* X1w, const float* X2w, const float* uv1,
+                           const float* uv2, const float* inv1, const float* inv2, const float* poses, const float* K,
+                           float th2, double* S, uint8_t* keep, int32_t* stats, LmBranches* br) {
     Sim3OptInput in;
     in.n = n; in.valid = valid; in.X1w = X1w; in.X2w = X2w; in.uv1 = uv1; in.uv2 = uv2; in.inv1 = inv1;
     in.inv2 = inv2;
@@ -615,9 +634,26 @@ int ora_optimize_sim3(int n, const uint8_t* valid, const float* X1w, const float
     Sim3Est e;
     std::memcpy(e.q, S, 32); std::memcpy(e.t, S + 4, 24); e.s = S[7];
     Sim3OptStats st{};
-    const int r = optimize_sim3(in, e, keep, &st);
+    const int r = optimize_sim3(in, e, keep, &st, br);
     std::memcpy(S, e.q, 32); std::memcpy(S + 4, e.t, 24); S[7] = e.s;
     if (stats) { stats[0] = st.n_correspondences; stats[1] = st.n_bad; stats[2] = st.lm_iterations; stats[3] = st.lm_trials; }
+    return r;
+}
+
+int ora_optimize_sim3(int n, const uint8_t* valid, const float* X1w, const float* X2w, const float* uv1,
+                      const float* uv2, const float* inv1, const float* inv2, const float* poses, const float* K,
+                      float th2, double* S, uint8_t* keep, int32_t* stats) {
+    return optimize_sim3_c(n, valid, X1w, X2w, uv1, uv2, inv1, inv2, poses, K, th2, S, keep, stats, nullptr);
+}
+
+// ora_optimize_sim3 plus the call's LM branch record (branches[11], as ora_pose_optimization_branches).
+int ora_optimize_sim3_branches(int n, const uint8_t* valid, const float* X1w, const float* X2w, const float* uv1,
+                               const float* uv2, const float* inv1, const float* inv2, const float* poses,
+                               const float* K, float th2, double* S, uint8_t* keep, int32_t* stats,
+                               int32_t* branches) {
+    LmBranches br{};
+    const int r = optimize_sim3_c(n, valid, X1w, X2w, uv1, uv2, inv1, inv2, poses, K, th2, S, keep, stats, &br);
+    std::memcpy(branches, &br, sizeof(br));
     return r;
 }
 

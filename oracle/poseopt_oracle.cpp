@@ -345,6 +345,7 @@ struct Problem {
     double lambda = -1.0, ni = 2.0;
     int nBadLM = 0;
     PoseOptStats st = {0, 0, 0};
+    LmBranches* br = nullptr;  // optional branch record (lm_branches.h): counts only
 
     double active_robust_chi2() const {
         double chi = 0.0;
@@ -437,6 +438,7 @@ struct Problem {
         st.lm_iterations++;
         compute_active_errors(est);
         double currentChi = active_robust_chi2();
+        if (br && !std::isfinite(currentChi)) br->currentchi_nonfinite++;
         double tempChi = currentChi;
         const double iniChi = currentChi;
         double H[6][6], b[6];
@@ -464,12 +466,22 @@ struct Problem {
             est = se3_mul(se3_exp(x), est);  // update -> VertexSE3Expmap::oplusImpl
             compute_active_errors(est);
             tempChi = active_robust_chi2();
+            if (br) {
+                br->trials++;
+                if (!ok2) br->not_ok2++;
+                if (!std::isfinite(tempChi)) br->tempchi_nonfinite++;
+            }
             if (!ok2) tempChi = std::numeric_limits<double>::max();
             rho = (currentChi - tempChi);
             double scale = 0.;
             for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + b[j]);
             scale += 1e-3;
             rho /= scale;
+            if (br) {
+                if (rho != rho) br->rho_nan++;
+                if (!(rho > 0 && std::isfinite(tempChi))) br->rejected++;
+                else if (!ok2) br->not_ok2_accepted++;
+            }
             if (rho > 0 && std::isfinite(tempChi)) {
                 double alpha = 1. - cube(2 * rho - 1);
                 alpha = std::min(alpha, 2. / 3.);
@@ -484,9 +496,12 @@ struct Problem {
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
+        if (br && qmax == 10) br->end_qmax++;
+        if (br && qmax != 10 && rho == 0) br->end_rho0++;
         if (qmax == 10 || rho == 0) return Terminate;
         if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
         else nBadLM = 0;
+        if (br && nBadLM >= 3) br->end_nbad++;
         if (nBadLM >= 3) return Terminate;
         return OK;
     }
@@ -495,6 +510,7 @@ struct Problem {
     void optimize(int iterations, SE3& est) {
         bool any = false;
         for (const Edge& e : edges) any |= (e.level == 0);
+        if (br && !any) br->no_active_edge++;
         if (!any) return;  // no active vertex: "0 vertices to optimize", returns -1
         bool ok = true;
         for (int i = 0; i < iterations && ok; i++) ok = (lm_solve(i, est) == OK);
@@ -503,8 +519,10 @@ struct Problem {
 
 }  // namespace
 
-int pose_optimization(const PoseOptInput& in, float Tcw_out[16], uint8_t* outlier, PoseOptStats* stats) {
+int pose_optimization(const PoseOptInput& in, float Tcw_out[16], uint8_t* outlier, PoseOptStats* stats,
+                      LmBranches* branches) {
     Problem P;
+    P.br = branches;
     P.K = {(double)in.fx, (double)in.fy, (double)in.cx, (double)in.cy, (double)in.bf};
     const float deltaMono = std::sqrt(5.991);
     const float deltaStereo = std::sqrt(7.815);

@@ -25,6 +25,7 @@
 // correctly rounded cube, Isometry3f::rotation() as linear().
 #pragma once
 #include <cstdint>
+#include "lm_branches.h"
 
 namespace rsc_oracle {
 
@@ -48,6 +49,8 @@ struct PoseOptStats {
 
 // Returns nInitialCorrespondences - nBad (0 without touching Tcw_out when fewer than 3 edges).
 // outlier[i] is written for slots with a map point (mvbOutlier), left untouched otherwise.
-int pose_optimization(const PoseOptInput& in, float Tcw_out[16], uint8_t* outlier, PoseOptStats* stats);
+// branches (optional): the LM branch record of this call (lm_branches.h), added to, not cleared.
+int pose_optimization(const PoseOptInput& in, float Tcw_out[16], uint8_t* outlier, PoseOptStats* stats,
+                      LmBranches* branches = nullptr);
 
 }  // namespace rsc_oracle

@@ -311,6 +311,7 @@ struct Problem {
     double lambda = -1.0, ni = 2.0;
     int nBadLM = 0;
     Sim3OptStats st = {0, 0, 0, 0};
+    LmBranches* br = nullptr;  // optional branch record (lm_branches.h): counts only
 
     void compute_active_errors(const Sim3& S) {
         const Sim3 Si = sim3_inverse(S);
@@ -381,6 +382,7 @@ struct Problem {
         st.lm_iterations++;
         compute_active_errors(S);
         double currentChi = active_robust_chi2();
+        if (br && !std::isfinite(currentChi)) br->currentchi_nonfinite++;
         double tempChi = currentChi;
         const double iniChi = currentChi;
         double H[7][7], b[7];
@@ -408,12 +410,22 @@ struct Problem {
             S = oplus(x, S);  // _optimizer->update(x): zeroes x[6] in place
             compute_active_errors(S);
             tempChi = active_robust_chi2();
+            if (br) {
+                br->trials++;
+                if (!ok2) br->not_ok2++;
+                if (!std::isfinite(tempChi)) br->tempchi_nonfinite++;
+            }
             if (!ok2) tempChi = std::numeric_limits<double>::max();
             rho = (currentChi - tempChi);
             double scale = 0.;
             for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + b[j]);
             scale += 1e-3;
             rho /= scale;
+            if (br) {
+                if (rho != rho) br->rho_nan++;
+                if (!(rho > 0 && std::isfinite(tempChi))) br->rejected++;
+                else if (!ok2) br->not_ok2_accepted++;
+            }
             if (rho > 0 && std::isfinite(tempChi)) {
                 double alpha = 1. - cube(2 * rho - 1);
                 alpha = std::min(alpha, 2. / 3.);
@@ -428,9 +440,12 @@ struct Problem {
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
+        if (br && qmax == 10) br->end_qmax++;
+        if (br && qmax != 10 && rho == 0) br->end_rho0++;
         if (qmax == 10 || rho == 0) return Terminate;
         if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
         else nBadLM = 0;
+        if (br && nBadLM >= 3) br->end_nbad++;
         if (nBadLM >= 3) return Terminate;
         return OK;
     }
@@ -439,6 +454,7 @@ struct Problem {
     void optimize(int iterations, Sim3& S) {
         bool any = false;
         for (const Edge& e : edges) any |= e.active;
+        if (br && !any) br->no_active_edge++;
         if (!any) return;  // "0 vertices to optimize": returns -1
         bool ok = true;
         for (int i = 0; i < iterations && ok; i++) ok = (lm_solve(i, S) == OK);
@@ -447,8 +463,9 @@ struct Problem {
 
 }  // namespace
 
-int optimize_sim3(const Sim3OptInput& in, Sim3Est& S_io, uint8_t* keep, Sim3OptStats* stats) {
+int optimize_sim3(const Sim3OptInput& in, Sim3Est& S_io, uint8_t* keep, Sim3OptStats* stats, LmBranches* branches) {
     Problem P;
+    P.br = branches;
     P.K1 = {{(double)in.K1[0], (double)in.K1[1]}, {(double)in.K1[2], (double)in.K1[3]}};
     P.K2 = {{(double)in.K2[0], (double)in.K2[1]}, {(double)in.K2[2], (double)in.K2[3]}};
     const float deltaHuber = std::sqrt(in.th2);  // float sqrt (Optimizer.cpp:1104)

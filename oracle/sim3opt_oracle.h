@@ -29,6 +29,7 @@
 // (rsc_math.h), exp(0) = 1.
 #pragma once
 #include <cstdint>
+#include "lm_branches.h"
 
 namespace rsc_oracle {
 
@@ -61,6 +62,8 @@ struct Sim3OptStats {
 
 // Returns nIn (0 when nCorrespondences - nBad < 10; g2oS12 is then left unchanged).  keep[i] = 0
 // where vpMatches1[i] is set to NULL (outliers), 1 elsewhere.  S: g2oS12 in / out.
-int optimize_sim3(const Sim3OptInput& in, Sim3Est& S, uint8_t* keep, Sim3OptStats* stats);
+// branches (optional): the LM branch record of this call (lm_branches.h), added to, not cleared.
+int optimize_sim3(const Sim3OptInput& in, Sim3Est& S, uint8_t* keep, Sim3OptStats* stats,
+                  LmBranches* branches = nullptr);
 
 }  // namespace rsc_oracle

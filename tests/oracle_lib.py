@@ -62,6 +62,9 @@ def lib():
                                               C.c_float, f32p, f32p, u8p, i32p, C.c_void_p, C.c_float]
     L.ora_optimize_sim3.argtypes = [C.c_int, u8p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_float,
                                     np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS"), u8p, i32p]
+    L.ora_pose_optimization_branches.argtypes = L.ora_pose_optimization.argtypes + [i32p]
+    L.ora_pose_optimization_branches.restype = C.c_int
+    L.ora_optimize_sim3_branches.argtypes = L.ora_optimize_sim3.argtypes + [i32p]
     L.ora_glibc_rand.argtypes = [C.c_uint32, C.c_int, i32p]
     L.ora_sample_stream.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, i32p]
     L.ora_pnp_create.restype = vp
@@ -416,9 +419,19 @@ class OracleMLPnP:
         return out[:n].astype(bool)
 
 
-def pose_optimization(frame):
+# Fields of the LM branch record (oracle/lm_branches.h), in order.
+LM_BRANCH_FIELDS = ("trials", "not_ok2", "tempchi_nonfinite", "rho_nan", "rejected", "end_qmax", "end_rho0",
+                    "end_nbad", "no_active_edge", "currentchi_nonfinite", "not_ok2_accepted")
+
+
+def _branch_dict(br):
+    return {k: int(v) for k, v in zip(LM_BRANCH_FIELDS, br)}
+
+
+def pose_optimization(frame, branches=None):
     """Optimizer::PoseOptimization on the oracle: (nGood, Tcw float32[4,4], outlier uint8[n], stats[3]).
-    outlier slots without a map point are 255 (untouched)."""
+    outlier slots without a map point are 255 (untouched).  branches: an int32[11] array that receives
+    the call's LM branch record (pose_optimization_branches)."""
     L = lib()
     n = frame.n
     T = np.zeros(16, np.float32)
@@ -426,15 +439,21 @@ def pose_optimization(frame):
     st = np.zeros(3, np.int32)
     ur = getattr(frame, "u_right", None)
     ur = None if ur is None else np.ascontiguousarray(ur, np.float32)
-    r = L.ora_pose_optimization(n, np.ascontiguousarray(frame.has_mp, np.uint8),
-                                np.ascontiguousarray(frame.uv, np.float32),
-                                np.ascontiguousarray(frame.Xw, np.float32),
-                                np.ascontiguousarray(frame.inv_sigma2, np.float32), frame.fx, frame.fy, frame.cx,
-                                frame.cy, np.ascontiguousarray(frame.Tcw, np.float32).reshape(16), T, out, st,
-                                None if ur is None else ur.ctypes.data, float(getattr(frame, "bf", 0.0)))
+    args = (n, np.ascontiguousarray(frame.has_mp, np.uint8), np.ascontiguousarray(frame.uv, np.float32),
+            np.ascontiguousarray(frame.Xw, np.float32), np.ascontiguousarray(frame.inv_sigma2, np.float32),
+            frame.fx, frame.fy, frame.cx, frame.cy, np.ascontiguousarray(frame.Tcw, np.float32).reshape(16), T,
+            out, st, None if ur is None else ur.ctypes.data, float(getattr(frame, "bf", 0.0)))
+    r = L.ora_pose_optimization(*args) if branches is None else L.ora_pose_optimization_branches(*args, branches)
     if r == 0 and not T.any():
         T = np.ascontiguousarray(frame.Tcw, np.float32).reshape(16).copy()
     return r, T.reshape(4, 4), out, st
+
+
+def pose_optimization_branches(frame):
+    """pose_optimization plus the LM branch record of the call: (nGood, Tcw, outlier, stats, dict over
+    LM_BRANCH_FIELDS).  The results are the ones pose_optimization returns (the record only counts)."""
+    br = np.zeros(len(LM_BRANCH_FIELDS), np.int32)
+    return (*pose_optimization(frame, br), _branch_dict(br))
 
 
 class OracleBow:
@@ -566,18 +585,27 @@ def l1_score(ids1, v1, ids2, v2) -> float:
                               np.ascontiguousarray(v2, np.float64))
 
 
-def optimize_sim3(p):
+def optimize_sim3(p, branches=None):
     """Optimizer::OptimizeSim3 on the oracle for a rsc.synth.Sim3OptProblem: (nIn, S float64[8] = q (x, y,
-    z, w), t, s after the call, keep uint8[n] (0 where vpMatches1[i] is set to NULL), stats[4])."""
+    z, w), t, s after the call, keep uint8[n] (0 where vpMatches1[i] is set to NULL), stats[4]).
+    branches: an int32[11] array that receives the call's LM branch record (optimize_sim3_branches)."""
     n = p.n
     S = np.ascontiguousarray(p.S0, np.float64).copy()
     keep = np.zeros(max(n, 1), np.uint8)
     st = np.zeros(4, np.int32)
-    r = lib().ora_optimize_sim3(n, np.ascontiguousarray(p.valid, np.uint8), np.ascontiguousarray(p.X1w, np.float32),
-                                np.ascontiguousarray(p.X2w, np.float32), np.ascontiguousarray(p.uv1, np.float32),
-                                np.ascontiguousarray(p.uv2, np.float32), np.ascontiguousarray(p.inv1, np.float32),
-                                np.ascontiguousarray(p.inv2, np.float32), p.poses24(), p.K8(), float(p.th2), S, keep, st)
+    args = (n, np.ascontiguousarray(p.valid, np.uint8), np.ascontiguousarray(p.X1w, np.float32),
+            np.ascontiguousarray(p.X2w, np.float32), np.ascontiguousarray(p.uv1, np.float32),
+            np.ascontiguousarray(p.uv2, np.float32), np.ascontiguousarray(p.inv1, np.float32),
+            np.ascontiguousarray(p.inv2, np.float32), p.poses24(), p.K8(), float(p.th2), S, keep, st)
+    r = lib().ora_optimize_sim3(*args) if branches is None else lib().ora_optimize_sim3_branches(*args, branches)
     return r, S, keep[:n], st
+
+
+def optimize_sim3_branches(p):
+    """optimize_sim3 plus the LM branch record of the call: (nIn, S, keep, stats, dict over
+    LM_BRANCH_FIELDS)."""
+    br = np.zeros(len(LM_BRANCH_FIELDS), np.int32)
+    return (*optimize_sim3(p, br), _branch_dict(br))
 
 
 def libc_srand(seed: int):

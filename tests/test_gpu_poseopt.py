@@ -1,6 +1,10 @@
 """GPU: rsc_pose_optimization_many (Optimizer::PoseOptimization on the MI355X) == the oracle, bit for
 bit (pose bits, nGood, mvbOutlier flags, LM iteration and trial counts), across sizes, outlier
-ratios, slots without map points, the < 3 and < 10 edge rules and a 64-frame batch."""
+ratios, slots without map points, the < 3 and < 10 edge rules and a 64-frame batch.
+
+Every input here is a frustum scene of rsc/synth.py: none makes the LDLT fail or a chi2 non-finite, and
+no edge count is a multiple of the 256-edge slab.  Those branches, the slab boundaries and the
+8192-edge limit are in tests/test_gpu_lm_edges.py (cases: tests/lm_edge_cases.py)."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,11 @@
 """GPU: rsc_optimize_sim3_many (Optimizer::OptimizeSim3 on the MI355X) == the oracle, bit for bit
 (nIn, g2oS12 quaternion / translation / scale bits, the NULLed vpMatches1 entries, LM iteration and
 trial counts), across sizes, outlier ratios, the < 10 rule, empty problems and a 32-pair batch, in
-both forms (one workgroup per pair; the cooperative form with helper workgroups, the default)."""
+both forms (one workgroup per pair; the cooperative form with helper workgroups, the default).
+
+Every input here is a generated loop-closure pair: none makes the LDLT fail or a chi2 non-finite.
+Those branches, the 64-edge chunk and 192-edge slab boundaries and the 8192-correspondence limit are
+in tests/test_gpu_lm_edges.py (cases: tests/lm_edge_cases.py)."""
 import numpy as np
 import pytest
 
