@@ -2,7 +2,11 @@
 overload) through the C ABI (rsc_bow_create / rsc_search_by_bow_*_many) against the oracle: match
 vectors and counts bit-exact, on the golden fixtures, relocalization- and loop-closure-shaped
 batches, and the edge cases (empty views, no common nodes, nodes wider than a wavefront, maximum
-view size, descriptor ties, invalid map points, refreshed validity)."""
+view size, descriptor ties, invalid map points, refreshed validity).
+
+The views here are random, so the ratio test is never close and no two features contend for one
+match: contested nodes, rescans, exact thresholds and ties, ratio edges and thousands of nodes are in
+tests/test_gpu_bow_walk.py."""
 import os
 
 import numpy as np
