@@ -10,7 +10,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fa
 HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
-     facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu
+     facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test
 
 $(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
@@ -44,6 +44,10 @@ $(LIBDIR)/kfproj.o: $(CSRC)/kfproj.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/localproj.o: $(CSRC)/localproj.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/kfdb.o: $(CSRC)/kfdb.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -56,7 +60,7 @@ $(LIBDIR)/rsc_api.o: $(CSRC)/rsc_api.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 # TEST-ONLY variant: the split eigen stage's hand-off waits give up after one poll, so the fault path
@@ -65,7 +69,7 @@ $(LIBDIR)/kernels_spin1.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DRSC_SPLIT_SPIN_LIMIT=1 -c $< -o $@
 
-$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 facade_test: $(LIBDIR)/facade_test
@@ -82,6 +86,11 @@ facade_loopproj_test: $(LIBDIR)/facade_loopproj_test
 
 $(LIBDIR)/facade_loopproj_test: tests/cpp/facade_loopproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
 	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_loopproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+
+facade_localproj_test: $(LIBDIR)/facade_localproj_test
+
+$(LIBDIR)/facade_localproj_test: tests/cpp/facade_localproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
+	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_localproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
 
 facade_voc_test: $(LIBDIR)/facade_voc_test
 
@@ -117,8 +126,12 @@ kfproj_emu:
 bowvoc_emu:
 	$(MAKE) -s -C tests/bowvoc_emu
 
-clean:
-	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build
+localproj_emu:
+	$(MAKE) -s -C tests/localproj_emu
 
-.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu facade_test facade_proj_test facade_loopproj_test \
+clean:
+	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
+	       tests/localproj_emu/build
+
+.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu facade_localproj_test facade_test facade_proj_test facade_loopproj_test \
         facade_voc_test chase_mirror_test clean

@@ -683,6 +683,61 @@ int rsc_loop_verify_many(rsc_context* ctx, rsc_kfview* const* kf_cur, rsc_kfview
                          const int32_t* const* matches, const uint8_t* const* already,
                          rsc_loop_verify_result* out, int32_t* const* projected);
 
+/* ---- Tracking::SearchLocalPoints: the frustum test and the local-map projection matcher -------------
+ * Tracking::SearchLocalPoints (src/Tracking.cpp:1003-1028) = Frame::isInFrustum(pMP, 0.5)
+ * (src/Frame.cpp:336-392) over mvpLocalMapPoints, then ORBmatcher::SearchByProjection(Frame&,
+ * vector<MapPoint>&, th) (src/ORBmatcher.cpp:16-100), over a resident Frame (rsc_frameview with
+ * rsc_frameview_set_stereo) and a flat MapPoint list (rsc_mpview).  Every point in view takes, among the
+ * Frame features of levels [L-1, L] inside r * th * scale[L] of its projection (r = 2.5 when viewCos >
+ * 0.998, else 4.0) that pass the stereo gate and hold no MapPoint with observations, the one with the
+ * smallest descriptor distance, if that is <= TH_HIGH = 100 and not vetoed by the runner-up (same level,
+ * bestDist > nn_ratio * bestDist2).  A feature taken by an earlier point of the call is skipped only when
+ * that point has observations; otherwise a later point may take it again and overwrite it (both count).
+ * The reference's sequential order is reproduced exactly.  Precondition: no eligible point projects to a
+ * NaN pixel (camera z == 0 with x == 0 or y == 0, undefined in the reference); such a point is skipped. */
+typedef struct {
+    int32_t in_view;  /* mbTrackInView */
+    float proj_x;     /* mTrackProjX */
+    float proj_y;     /* mTrackProjY */
+    float proj_xr;    /* mTrackProjXR */
+    int32_t level;    /* mnTrackScaleLevel */
+    float view_cos;   /* mTrackViewCos */
+} rsc_track_record;
+
+/* The Frame's mvuRight (view n entries, negative for a monocular feature) and mbf: isInFrustum writes
+ * mTrackProjXR = u - mbf / z and the matcher's stereo gate reads both; rsc_frame_features carries none. */
+int rsc_frameview_set_stereo(rsc_frameview* view, const float* u_right, float mbf);
+
+/* Tracking.cpp:1003-1028 for c < count in one launch (one workgroup per problem).  Tcw [count][16]:
+ * mCurrentFrame.mTcw, row-major.  skip[c][i] (points[c] n entries): mnLastFrameSeen == mCurrentFrame.mnId
+ * (:1006); isBad() is the view's state.  has_obs[c][i]: Observations() > 0 of point i.  frame_occ[c][f]
+ * (frames[c] n entries): 0 = F.mvpMapPoints[f] is NULL on entry, 1 = set with Observations() == 0, 2 = set
+ * with Observations() > 0.  cos_limit = viewingCosLimit (0.5), th and nn_ratio as the reference's call
+ * (nn_ratio >= 0).  out[c][f]: index into points[c] of the MapPoint the call leaves in F.mvpMapPoints[f],
+ * else -1 (an entry occupant that nobody overwrote is not reported).  track[c][i] (out): what isInFrustum
+ * leaves in point i, for the caller's mbTrackInView... write-back and IncreaseVisible (in_view = 0 and
+ * zeros for a point that is skipped, bad or outside).  n_to_match[c] = nToMatch; nmatches[c] = the
+ * matcher's return value (the reference skips the matcher when nToMatch == 0, which returns 0 here too);
+ * rounds (may be NULL): fixed-point rounds run (diagnostic).  A Frame with n > 8192 or without
+ * rsc_frameview_set_stereo is RSC_ERR_ARG; count == 0 and empty point lists are RSC_OK.  With timing
+ * enabled, rsc_context_last_kernel_timing gives [0] the setup kernel, [1] the rounds kernel, [2] both (ms). */
+int rsc_search_local_points_many(rsc_context* ctx, rsc_frameview* const* frames, rsc_mpview* const* points,
+                                 int count, const float* Tcw, const uint8_t* const* skip,
+                                 const uint8_t* const* has_obs, const uint8_t* const* frame_occ, float cos_limit,
+                                 float th, float nn_ratio, int32_t* const* out, rsc_track_record* const* track,
+                                 int32_t* nmatches, int32_t* n_to_match, int32_t* rounds);
+
+/* The bare ORBmatcher::SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cpp:16-100): as above with
+ * track[c][i] as an INPUT holding the host's mbTrackInView, mTrackProjX / Y / XR, mnTrackScaleLevel and
+ * mTrackViewCos (a level outside [0, n_levels) on a point in view is RSC_ERR_ARG).  A point with skip[c][i]
+ * set is left out like one with mbTrackInView false.  n_to_match[c] = the points that reach the window. */
+int rsc_search_by_projection_points_many(rsc_context* ctx, rsc_frameview* const* frames,
+                                         rsc_mpview* const* points, int count, const uint8_t* const* skip,
+                                         const uint8_t* const* has_obs, const uint8_t* const* frame_occ, float th,
+                                         float nn_ratio, int32_t* const* out,
+                                         const rsc_track_record* const* track, int32_t* nmatches,
+                                         int32_t* n_to_match, int32_t* rounds);
+
 /* ---- KeyFrameDatabase: BoW candidate scoring (src/KeyFrameDatabase.cpp) ---------------------- */
 /* A device-resident keyframe database: each KeyFrame is a slot in [0, capacity) holding its
  * BowVector (word ids ascending, TF-IDF values, DBoW2 L1_NORM scoring), its

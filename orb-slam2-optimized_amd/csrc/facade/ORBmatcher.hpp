@@ -29,6 +29,13 @@
 // does plus mvKeysUn[i].angle, and of the Frame only public members (include/Frame.hpp): N, mvKeysUn,
 // mDescriptors, mGrid, mnMinX..mnMaxY, mfGridElementWidthInv/HeightInv, fx..cy, mvScaleFactors,
 // mnScaleLevels, mfLogScaleFactor, mTcw (rotation() / translation()) and mvpMapPoints, which it writes.
+//
+// SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cpp:16-100; Tracking.cpp:1027) and the helper
+// rsc_orb::SearchLocalPoints (Tracking.cpp:1003-1028) additionally read the Frame's mvuRight, mbf and mnId,
+// and per MapPoint Observations(), GetNormal(), mnLastFrameSeen and the track members mbTrackInView,
+// mTrackProjX, mTrackProjY, mTrackProjXR, mnTrackScaleLevel, mTrackViewCos; the helper writes those back and
+// calls IncreaseVisible().  The points must be distinct and non-null (mvpLocalMapPoints is built through
+// mnTrackReferenceForFrame, Tracking.cpp:1041-1062, which guarantees both).
 #pragma once
 #include <algorithm>
 #include <memory>
@@ -688,7 +695,87 @@ public:
         return std::vector<int>(nf.begin(), nf.begin() + C);
     }
 
+    // SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cpp:16-100; Tracking.cpp:1027): every MapPoint with
+    // mbTrackInView that is not bad is matched around (mTrackProjX, mTrackProjY) at levels
+    // [mnTrackScaleLevel - 1, mnTrackScaleLevel]; the matches are written to F.mvpMapPoints, returns their
+    // number (a feature taken twice, by a point without observations and then by a later one, counts twice).
+    template <class FrameT, class MPPtr>
+    int SearchByProjection(FrameT& F, const std::vector<MPPtr>& vpMapPoints, const float th) {
+        return local_points(F, vpMapPoints, th, mfNNratio, false, 0.f, nullptr);
+    }
+
+    // Tracking::SearchLocalPoints from :1003 on (Tracking.cpp:1003-1028) in one device call: isInFrustum(pMP,
+    // 0.5) over the points with mnLastFrameSeen != F.mnId that are not bad, the track members and
+    // IncreaseVisible() on the MapPoints as the reference leaves them, then the matcher when nToMatch > 0.
+    // The loop over F.mvpMapPoints before it (:982-998) stays with the caller.  Returns the matcher's count.
+    template <class FrameT, class MPPtr>
+    static int SearchLocalPoints(FrameT& F, const std::vector<MPPtr>& vpLocalMapPoints, float th, float nnratio,
+                                 int* nToMatch = nullptr) {
+        return local_points(F, vpLocalMapPoints, th, nnratio, true, 0.5f, nToMatch);
+    }
+
 private:
+    template <class FrameT, class MPPtr>
+    static int local_points(FrameT& F, const std::vector<MPPtr>& vpMapPoints, float th, float nnratio, bool fused,
+                            float cos_limit, int* nToMatch) {
+        LoopMapPoints<MPPtr> view(vpMapPoints);  // state 2 = isBad() (:28 / Tracking.cpp:1008)
+        detail::FrameViewUpload fv = detail::upload_frameview(F);
+        check(rsc_frameview_set_stereo(fv.h, F.mvuRight.data(), F.mbf), "rsc_frameview_set_stereo");
+        const size_t np = vpMapPoints.size(), nf = (size_t)fv.n;
+        std::vector<uint8_t> skip(np > 0 ? np : 1, 0), has_obs(np > 0 ? np : 1, 0), occ(nf > 0 ? nf : 1, 0);
+        std::vector<rsc_track_record> track(np > 0 ? np : 1);
+        for (size_t i = 0; i < np; ++i) {
+            auto& mp = *vpMapPoints[i];
+            has_obs[i] = mp.Observations() > 0 ? 1 : 0;
+            if (fused) {
+                skip[i] = mp.mnLastFrameSeen == F.mnId ? 1 : 0;  // Tracking.cpp:1006
+                track[i] = rsc_track_record{0, 0.f, 0.f, 0.f, 0, 0.f};
+            } else {
+                track[i] = rsc_track_record{mp.mbTrackInView ? 1 : 0, mp.mTrackProjX, mp.mTrackProjY, mp.mTrackProjXR,
+                                            (int32_t)mp.mnTrackScaleLevel, mp.mTrackViewCos};
+            }
+        }
+        for (size_t f = 0; f < nf && f < F.mvpMapPoints.size(); ++f)  // :58-60
+            if (F.mvpMapPoints[f]) occ[f] = F.mvpMapPoints[f]->Observations() > 0 ? 2 : 1;
+        std::vector<int32_t> out(nf > 0 ? nf : 1, -1);
+        float T[16];
+        if (fused) iso_to_array(F.mTcw, T);
+        rsc_frameview* hf = fv.h;
+        rsc_mpview* hp = view.handle();
+        const uint8_t* pskip = skip.data();
+        const uint8_t* pobs = has_obs.data();
+        const uint8_t* pocc = occ.data();
+        int32_t* pout = out.data();
+        rsc_track_record* ptr = track.data();
+        const rsc_track_record* cptr = track.data();
+        int32_t nm = 0, ntm = 0;
+        if (fused)
+            check(rsc_search_local_points_many(thread_context(), &hf, &hp, 1, T, &pskip, &pobs, &pocc, cos_limit, th,
+                                               nnratio, &pout, &ptr, &nm, &ntm, nullptr),
+                  "SearchLocalPoints");
+        else
+            check(rsc_search_by_projection_points_many(thread_context(), &hf, &hp, 1, &pskip, &pobs, &pocc, th, nnratio,
+                                                       &pout, &cptr, &nm, &ntm, nullptr),
+                  "SearchByProjection(Frame, vpMapPoints)");
+        if (fused)
+            for (size_t i = 0; i < np; ++i) {
+                auto& mp = *vpMapPoints[i];
+                if (skip[i] || mp.isBad()) continue;       // Tracking.cpp:1006-1009: isInFrustum did not run
+                mp.mbTrackInView = track[i].in_view != 0;  // Frame.cpp:338 / :384
+                if (!track[i].in_view) continue;
+                mp.mTrackProjX = track[i].proj_x;
+                mp.mTrackProjXR = track[i].proj_xr;
+                mp.mTrackProjY = track[i].proj_y;
+                mp.mnTrackScaleLevel = track[i].level;
+                mp.mTrackViewCos = track[i].view_cos;
+                mp.IncreaseVisible();                      // Tracking.cpp:1013
+            }
+        for (size_t f = 0; f < nf && f < F.mvpMapPoints.size(); ++f)  // F.mvpMapPoints[bestIdx] = pMP (:94)
+            if (out[f] >= 0) F.mvpMapPoints[f] = vpMapPoints[out[f]];
+        if (nToMatch) *nToMatch = ntm;
+        return nm;
+    }
+
     // one upload per distinct KeyFrame object; ki[c] = its view
     template <class KFPtr>
     static void upload_distinct(const std::vector<KFPtr>& vpKFs, std::vector<detail::KFViewUpload>& views,
@@ -722,5 +809,13 @@ private:
     float mfNNratio;
     bool mbCheckOrientation;
 };
+
+// Tracking::SearchLocalPoints from :1003 on (ORBmatcher::SearchLocalPoints above); the reference calls the
+// matcher with ORBmatcher(0.8) and th = 1, 3 (RGB-D) or 5 (just relocalised).
+template <class FrameT, class MPPtr>
+int SearchLocalPoints(FrameT& F, const std::vector<MPPtr>& vpLocalMapPoints, float th, float nnratio = 0.8f,
+                      int* nToMatch = nullptr) {
+    return ORBmatcher::SearchLocalPoints(F, vpLocalMapPoints, th, nnratio, nToMatch);
+}
 
 }  // namespace rsc_orb

@@ -26,6 +26,7 @@
 #include "rsc_sim3match.h"
 #include "rsc_frameproj.h"
 #include "rsc_kfproj.h"
+#include "rsc_localproj.h"
 #include "rsc_sim3compose.h"
 #include "rsc_kfdb.h"
 #include "rsc_bowvoc.h"
@@ -2707,6 +2708,9 @@ struct rsc_frameview {
     std::vector<float> kp, inv_level_sigma2;
     std::vector<int32_t> octave;
     float K[4];
+    DevBuf<float> d_uright;  // mvuRight (rsc_frameview_set_stereo)
+    float mbf = 0.0f;
+    bool has_stereo = false;
 };
 
 int rsc_frameview_create(rsc_context* C, const rsc_frame_features* f, rsc_frameview** out) {
@@ -2785,6 +2789,17 @@ int rsc_kfview_set_angles(rsc_kfview* v, const float* angle) {
     RSC_HIP(hipStreamSynchronize(v->ctx->stream));
     if (v->n) RSC_HIP(hipMemcpy(v->d_angle.p, angle, 4 * (size_t)v->n, hipMemcpyHostToDevice));
     v->has_angles = true;
+    return RSC_OK;
+}
+
+int rsc_frameview_set_stereo(rsc_frameview* v, const float* u_right, float mbf) {
+    if (!v || (v->n > 0 && !u_right)) return RSC_ERR_ARG;
+    RSC_HIP(hipSetDevice(v->ctx->device));
+    if (int e = v->d_uright.ensure((size_t)std::max(v->n, 1))) return e;
+    RSC_HIP(hipStreamSynchronize(v->ctx->stream));
+    if (v->n) RSC_HIP(hipMemcpy(v->d_uright.p, u_right, 4 * (size_t)v->n, hipMemcpyHostToDevice));
+    v->mbf = mbf;
+    v->has_stereo = true;
     return RSC_OK;
 }
 
@@ -4529,5 +4544,151 @@ int rsc_loop_verify_many(rsc_context* C, rsc_kfview* const* kf_cur, rsc_kfview* 
         if (projected && projected[c] && n) std::memcpy(projected[c], outs[c].data(), 4 * (size_t)n);
     }
     return RSC_OK;
+}
+
+// ---- Tracking::SearchLocalPoints: isInFrustum + SearchByProjection(Frame&, vector<MapPoint>&, th) (rsc_localproj.h) ----
+namespace {
+static_assert(sizeof(rsc_track_record) == sizeof(LpTrack), "rsc_track_record layout");
+
+int local_points_impl(rsc_context* C, rsc_frameview* const* frames, rsc_mpview* const* points, int count,
+                      const float* Tcw, const uint8_t* const* skip, const uint8_t* const* has_obs,
+                      const uint8_t* const* frame_occ, float cos_limit, float th, float nn_ratio,
+                      int32_t* const* out, rsc_track_record* const* track, int32_t* nmatches, int32_t* n_to_match,
+                      int32_t* rounds, bool fused) {
+    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
+    if (!(nn_ratio >= 0.0f) || !(th == th)) {  // the candidate cache's bound needs a monotone veto
+        g_last_error = "nn_ratio must be >= 0";
+        return RSC_ERR_ARG;
+    }
+    if (count == 0) return RSC_OK;
+    if (!frames || !points || !skip || !has_obs || !frame_occ || !out || !track || (fused && !Tcw))
+        return RSC_ERR_ARG;
+    for (int c = 0; c < count; ++c) {
+        if (!frames[c] || !points[c] || frames[c]->ctx != C || points[c]->ctx != C) return RSC_ERR_ARG;
+        if (frames[c]->n > kLpMaxFeatures) {
+            g_last_error = "Frame with more than 8192 features";
+            return RSC_ERR_ARG;
+        }
+        if (!frames[c]->has_stereo) {
+            g_last_error = "Frame view without mvuRight / mbf (rsc_frameview_set_stereo)";
+            return RSC_ERR_ARG;
+        }
+        if (points[c]->n && (!skip[c] || !has_obs[c] || !track[c])) return RSC_ERR_ARG;
+        if (frames[c]->n && (!frame_occ[c] || !out[c])) return RSC_ERR_ARG;
+        if (!fused) {
+            const int n_levels = (int)frames[c]->inv_level_sigma2.size();
+            for (int i = 0; i < points[c]->n; ++i)
+                if (track[c][i].in_view && (track[c][i].level < 0 || track[c][i].level >= n_levels)) {
+                    g_last_error = "mnTrackScaleLevel out of range";
+                    return RSC_ERR_ARG;
+                }
+        }
+    }
+    // layout: problem table | skip | has_obs | frame_occ | track (matcher-only)  (uploaded)  | windows |
+    // candidates | claims  (scratch)  | track (fused) | out | nmatches, nToMatch, rounds  (what comes back)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    std::vector<size_t> o_sk(count), o_ho(count), o_oc(count), o_tr(count), o_rec(count), o_cd(count), o_cl(count),
+        o_out(count), o_cnt(count);
+    int max_points = 0;
+    size_t off = al(sizeof(LocalProjProblem) * count);
+    for (int c = 0; c < count; ++c) {
+        const size_t np = (size_t)std::max(points[c]->n, 1), nf = (size_t)std::max(frames[c]->n, 1);
+        o_sk[c] = off; off = al(off + np);
+        o_ho[c] = off; off = al(off + np);
+        o_oc[c] = off; off = al(off + nf);
+        if (!fused) { o_tr[c] = off; off = al(off + sizeof(LpTrack) * np); }
+    }
+    const size_t up = off;
+    for (int c = 0; c < count; ++c) {
+        const size_t np = (size_t)std::max(points[c]->n, 1);
+        o_rec[c] = off; off = al(off + sizeof(LpRec) * np);
+        o_cd[c] = off; off = al(off + sizeof(ProjCand) * np);
+        o_cl[c] = off; off = al(off + 4 * np);
+        max_points = std::max(max_points, points[c]->n);
+    }
+    const size_t back = off;
+    for (int c = 0; c < count; ++c) {
+        const size_t np = (size_t)std::max(points[c]->n, 1);
+        if (fused) { o_tr[c] = off; off = al(off + sizeof(LpTrack) * np); }
+        o_out[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
+        o_cnt[c] = off; off += 16;
+    }
+    const size_t bytes = al(off);
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = C->d_fp.ensure(bytes)) return e;
+    if (int e = C->h_fp.ensure(bytes)) return e;
+    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
+    char* h = C->h_fp.p;
+    char* d = C->d_fp.p;
+    for (int c = 0; c < count; ++c) {
+        const rsc_frameview& f = *frames[c];
+        const rsc_mpview& m = *points[c];
+        if (m.n) {
+            std::memcpy(h + o_sk[c], skip[c], (size_t)m.n);
+            std::memcpy(h + o_ho[c], has_obs[c], (size_t)m.n);
+            if (!fused) std::memcpy(h + o_tr[c], track[c], sizeof(LpTrack) * (size_t)m.n);
+        }
+        if (f.n) std::memcpy(h + o_oc[c], frame_occ[c], (size_t)f.n);
+        LocalProjProblem p;
+        p.F = f.hdr;
+        p.u_right = f.d_uright.p;
+        p.mbf = f.mbf;
+        p.P = m.dev;
+        if (fused) std::memcpy(p.Tcw, Tcw + 16 * (size_t)c, sizeof(p.Tcw));
+        else std::memset(p.Tcw, 0, sizeof(p.Tcw));
+        p.skip = reinterpret_cast<const uint8_t*>(d + o_sk[c]);
+        p.has_obs = reinterpret_cast<const uint8_t*>(d + o_ho[c]);
+        p.frame_occ = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
+        p.track = reinterpret_cast<LpTrack*>(d + o_tr[c]);
+        p.rec = reinterpret_cast<LpRec*>(d + o_rec[c]);
+        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+        p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+        std::memcpy(h + sizeof(LocalProjProblem) * c, &p, sizeof(p));
+    }
+    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
+    timing_begin(C, 3);
+    RSC_HIP(launch_search_local_points(count, max_points, reinterpret_cast<const LocalProjProblem*>(d), fused ? 1 : 0,
+                                       cos_limit, th, nn_ratio, C->timing ? C->ev[5] : nullptr, C->stream));
+    timing_begin(C, 4);
+    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    if (C->timing) {  // rsc_context_last_kernel_timing: [0] setup kernel, [1] rounds kernel, [2] both
+        float ms = 0, a = 0, b = 0;
+        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
+        (void)hipEventElapsedTime(&a, C->ev[3], C->ev[5]);
+        (void)hipEventElapsedTime(&b, C->ev[5], C->ev[4]);
+        C->last_ms[0] = a;
+        C->last_ms[1] = b;
+        C->last_ms[2] = ms;
+    }
+    for (int c = 0; c < count; ++c) {
+        if (frames[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)frames[c]->n);
+        if (fused && points[c]->n) std::memcpy(track[c], h + o_tr[c], sizeof(LpTrack) * (size_t)points[c]->n);
+        if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
+        if (n_to_match) std::memcpy(&n_to_match[c], h + o_cnt[c] + 4, 4);
+        if (rounds) std::memcpy(&rounds[c], h + o_cnt[c] + 8, 4);
+    }
+    return RSC_OK;
+}
+}  // namespace
+
+int rsc_search_local_points_many(rsc_context* C, rsc_frameview* const* frames, rsc_mpview* const* points, int count,
+                                 const float* Tcw, const uint8_t* const* skip, const uint8_t* const* has_obs,
+                                 const uint8_t* const* frame_occ, float cos_limit, float th, float nn_ratio,
+                                 int32_t* const* out, rsc_track_record* const* track, int32_t* nmatches,
+                                 int32_t* n_to_match, int32_t* rounds) {
+    return local_points_impl(C, frames, points, count, Tcw, skip, has_obs, frame_occ, cos_limit, th, nn_ratio, out,
+                             track, nmatches, n_to_match, rounds, true);
+}
+
+int rsc_search_by_projection_points_many(rsc_context* C, rsc_frameview* const* frames, rsc_mpview* const* points,
+                                         int count, const uint8_t* const* skip, const uint8_t* const* has_obs,
+                                         const uint8_t* const* frame_occ, float th, float nn_ratio,
+                                         int32_t* const* out, const rsc_track_record* const* track,
+                                         int32_t* nmatches, int32_t* n_to_match, int32_t* rounds) {
+    return local_points_impl(C, frames, points, count, nullptr, skip, has_obs, frame_occ, 0.0f, th, nn_ratio, out,
+                             const_cast<rsc_track_record* const*>(track), nmatches, n_to_match, rounds, false);
 }
 }  // extern "C"

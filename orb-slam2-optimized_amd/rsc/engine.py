@@ -59,6 +59,7 @@ EXPORTED = [
     "rsc_loop_verify_many",
     "rsc_voc_create", "rsc_voc_destroy", "rsc_voc_size", "rsc_voc_info", "rsc_voc_transform_many",
     "rsc_voc_last_kernel_timing", "rsc_bow_create_transformed",
+    "rsc_frameview_set_stereo", "rsc_search_local_points_many", "rsc_search_by_projection_points_many",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -267,6 +268,15 @@ class FrameView:
         _check(load_library().rsc_frameview_create(ctx.h, C.byref(k), C.byref(h)), "rsc_frameview_create")
         self.h = h
 
+    def set_stereo(self, u_right, mbf: float):
+        """The Frame's mvuRight (float32 [n], negative = monocular feature) and mbf (rsc_frameview_set_stereo):
+        what isInFrustum's mTrackProjXR and the stereo gate of the local-map matcher read."""
+        u = np.ascontiguousarray(u_right, np.float32).reshape(-1)
+        assert u.size == self.n
+        if not self.n:
+            u = np.zeros(1, np.float32)
+        _check(load_library().rsc_frameview_set_stereo(self.h, u, float(mbf)), "rsc_frameview_set_stereo")
+
     def close(self):
         if getattr(self, "h", None):
             load_library().rsc_frameview_destroy(self.h)
@@ -356,6 +366,56 @@ def search_by_projection_kf_many(ctx: Context, kfs, points, Scw, already, occupi
                                                            _ptrs(oc), int(th), _ptrs(out), nm, rounds),
            "rsc_search_by_projection_kf_many")
     return [o[:k.n] for o, k in zip(out, kfs)], nm[:c], rounds[:c]
+
+
+# rsc_track_record (include/rsc.h): what Frame::isInFrustum leaves in a MapPoint
+TRACK_RECORD = np.dtype([("in_view", np.int32), ("proj_x", np.float32), ("proj_y", np.float32),
+                         ("proj_xr", np.float32), ("level", np.int32), ("view_cos", np.float32)])
+
+
+def _local_points(ctx, frames, points, Tcw, skip, has_obs, frame_occ, cos_limit, th, nn_ratio, track):
+    c = len(frames)
+    u8 = lambda arrays, views: [np.ascontiguousarray(a, np.uint8) if v.n else np.zeros(1, np.uint8)
+                                for a, v in zip(arrays, views)]
+    sk, ho, oc = u8(skip, points), u8(has_obs, points), u8(frame_occ, frames)
+    out = [np.full(max(f.n, 1), -7, np.int32) for f in frames]
+    if track is None:
+        tr = [np.zeros(max(p.n, 1), TRACK_RECORD) for p in points]
+    else:
+        tr = [np.ascontiguousarray(t, TRACK_RECORD) if p.n else np.zeros(1, TRACK_RECORD)
+              for t, p in zip(track, points)]
+    nm, ntm, rounds = (np.zeros(max(c, 1), np.int32) for _ in range(3))
+    L = load_library()
+    if track is None:
+        T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(c, 16)) if c else np.zeros((1, 16), np.float32)
+        _check(L.rsc_search_local_points_many(ctx.h, _handles(frames), _handles(points), c, T, _ptrs(sk), _ptrs(ho),
+                                              _ptrs(oc), float(cos_limit), float(th), float(nn_ratio), _ptrs(out),
+                                              _ptrs(tr), nm, ntm, rounds), "rsc_search_local_points_many")
+    else:
+        _check(L.rsc_search_by_projection_points_many(ctx.h, _handles(frames), _handles(points), c, _ptrs(sk),
+                                                      _ptrs(ho), _ptrs(oc), float(th), float(nn_ratio), _ptrs(out),
+                                                      _ptrs(tr), nm, ntm, rounds),
+               "rsc_search_by_projection_points_many")
+    return dict(out=[o[:f.n] for o, f in zip(out, frames)], track=[t[:p.n] for t, p in zip(tr, points)],
+                nmatches=nm[:c], n_to_match=ntm[:c], rounds=rounds[:c])
+
+
+def search_local_points_many(ctx: Context, frames, points, Tcw, skip, has_obs, frame_occ, cos_limit: float = 0.5,
+                             th: float = 1.0, nn_ratio: float = 0.8):
+    """Tracking::SearchLocalPoints (Tracking.cpp:1003-1028): Frame::isInFrustum over the list, then
+    ORBmatcher::SearchByProjection(F, vpMapPoints, th), for each (FrameView with set_stereo, MPView, Tcw [4,4],
+    skip uint8 [points n], has_obs uint8 [points n], frame_occ uint8 [frame n]: 0 NULL / 1 set without
+    observations / 2 set with observations) in one launch.  Returns a dict of per-problem lists / arrays: out
+    (int32 [frame n]: index into the points of the MapPoint left in mvpMapPoints[f], or -1), track
+    (TRACK_RECORD [points n]), nmatches, n_to_match, rounds."""
+    return _local_points(ctx, frames, points, Tcw, skip, has_obs, frame_occ, cos_limit, th, nn_ratio, None)
+
+
+def search_by_projection_points_many(ctx: Context, frames, points, track, skip, has_obs, frame_occ, th: float = 1.0,
+                                     nn_ratio: float = 0.8):
+    """The bare ORBmatcher::SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cpp:16-100) on the host's track
+    members (TRACK_RECORD [points n] per problem, not modified); otherwise as search_local_points_many."""
+    return _local_points(ctx, frames, points, None, skip, has_obs, frame_occ, 0.0, th, nn_ratio, track)
 
 
 def fuse_sim3_many(ctx: Context, kfs, points, Scw, in_kf, th: float):
@@ -714,6 +774,11 @@ def load_library(path: str = LIB_PATH):
     L.rsc_loop_verify_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, f64p_,
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                        C.POINTER(LoopVerifyResult), C.POINTER(C.c_void_p)]
+    L.rsc_frameview_set_stereo.argtypes = [vp, f32p_, C.c_float]
+    L.rsc_search_local_points_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_] + \
+        [C.POINTER(C.c_void_p)] * 3 + [C.c_float] * 3 + [C.POINTER(C.c_void_p)] * 2 + [i32p] * 3
+    L.rsc_search_by_projection_points_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int] + \
+        [C.POINTER(C.c_void_p)] * 3 + [C.c_float] * 2 + [C.POINTER(C.c_void_p)] * 2 + [i32p] * 3
     L.rsc_voc_create.argtypes = [vp, C.POINTER(VocabularyNodes), C.POINTER(vp)]
     L.rsc_voc_destroy.argtypes = [vp]
     L.rsc_voc_destroy.restype = None
