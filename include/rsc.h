@@ -504,7 +504,10 @@ typedef struct {
 } rsc_sim3_kf;
 
 typedef struct rsc_kfview rsc_kfview;
-/* Upload a KeyFrame's SearchBySim3 inputs (keypoints, grid, descriptors, pose, MapPoints) to HBM. */
+/* Upload a KeyFrame's SearchBySim3 inputs (keypoints, grid, descriptors, pose, MapPoints) to HBM.
+ * RSC_ERR_ARG when a slot with mp_state == 1 has a non-finite mp_dmax or mp_dmin: PredictScale's
+ * (int)ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) would leave int's range, which is undefined
+ * in the reference (one platform yields INT_MIN, another saturates), so it is refused, not mirrored. */
 int rsc_kfview_create(rsc_context* ctx, const rsc_sim3_kf* kf, rsc_kfview** out);
 void rsc_kfview_destroy(rsc_kfview* view);
 
@@ -513,10 +516,19 @@ void rsc_kfview_destroy(rsc_kfview* view);
  * the MapPoint already in vpMatches12[i1] (GetIndexInKeyFrame(pKF2)), -1 for NULL, -2 for a
  * MapPoint not in KF2.  out12[c][i1]: the KF2 keypoint index of each new match
  * (vpMatches12[i1] = vpMapPoints2[idx2]), else -1; nfound[c] = the return value.
- * R12 [count][9] row-major, t12 [count][3]. */
+ * R12 [count][9] row-major, t12 [count][3].
+ * RSC_ERR_ARG, before any launch, when th is not finite or when, for either KeyFrame of a pair,
+ * th * scale_factors[n_levels - 1] * max(grid_w_inv, grid_h_inv) >= 2^30: GetFeaturesInArea's
+ * (int)ceil((u - mnMinX + r) * mfGridElementWidthInv) must stay inside int (the u term is below 64
+ * cells); outside it the reference's conversion is undefined and is refused, not mirrored. */
 int rsc_search_by_sim3_many(rsc_context* ctx, rsc_kfview* const* kf1, rsc_kfview* const* kf2, int count,
                             const float* R12, const float* t12, float th, const int32_t* const* matched12,
                             int32_t* const* out12, int32_t* nfound);
+/* Diagnostic: the two directions of pair `pair` of the most recent rsc_search_by_sim3_many on the
+ * context, before the agreement step: m1[n1] = vnMatch1 (the KF2 keypoint of each KF1 slot or -1),
+ * m2[n2] = vnMatch2.  n1 / n2 must equal that pair's kf1 / kf2 n.  RSC_ERR_ARG when the context's last
+ * call did not succeed (or there was none), or the index or sizes do not fit. */
+int rsc_diag_sim3match_directions(rsc_context* ctx, int pair, int32_t* m1, int n1, int32_t* m2, int n2);
 
 /* ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame, sAlreadyFound, th, ORBdist) ------------------
  * (src/ORBmatcher.cpp:1317-1444 with Frame::GetFeaturesInArea, src/Frame.cpp:394-447): the matcher of

@@ -723,6 +723,12 @@ int ora_search_by_sim3(const rsc_sim3_kf* k1, const rsc_sim3_kf* k2, const int32
     return search_by_sim3(to_kf(*k1), to_kf(*k2), matched12, R12, t12, th, out12);
 }
 
+int ora_search_by_sim3_trace(const rsc_sim3_kf* k1, const rsc_sim3_kf* k2, const int32_t* matched12, const float* R12,
+                             const float* t12, float th, int32_t* out12, int32_t* m1, int32_t* m2, int32_t* reason1,
+                             int32_t* reason2) {
+    return search_by_sim3_trace(to_kf(*k1), to_kf(*k2), matched12, R12, t12, th, out12, m1, m2, reason1, reason2);
+}
+
 int ora_predict_scale(float dmax, float dist, float log_scale_factor, int n_levels) {
     return predict_scale(dmax, dist, log_scale_factor, n_levels);
 }

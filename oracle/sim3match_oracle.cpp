@@ -47,24 +47,31 @@ std::vector<int> features_in_area(const Sim3KF& k, float x, float y, float r) {
 // One direction of the search (:992-1070 for KF1 -> KF2 with `src` = KF1, `dst` = KF2, R/t = R21/t21;
 // :1072-1150 for KF2 -> KF1).  Intrinsics are pKF1's in both directions (:951-954).
 void search_direction(const Sim3KF& src, const Sim3KF& dst, const float* Rsd, const float* tsd,
-                      const std::vector<uint8_t>& already, const Sim3KF& k1, float th, std::vector<int>& match) {
+                      const std::vector<uint8_t>& already, const Sim3KF& k1, float th, int32_t* match,
+                      int32_t* reason) {
     for (int i = 0; i < src.n; ++i) {
+        match[i] = -1;
+        reason[i] = kSim3NotSearched;
         if (src.mp_state[i] == 0 || already[i]) continue;  // !pMP || vbAlreadyMatched (:998)
         if (src.mp_state[i] == 2) continue;                // isBad (:1001)
         float pc[3], pd[3];
         rot_add(src.Rcw, src.mp_pos + 3 * i, src.tcw, pc);
         rot_add(Rsd, pc, tsd, pd);
+        reason[i] = kSim3Depth;
         if (pd[2] < 0.0) continue;  // depth (:1008)
         const float invz = (float)(1.0 / (double)pd[2]);
         const float x = pd[0] * invz;
         const float y = pd[1] * invz;
         const float u = k1.fx * x + k1.cx;
         const float v = k1.fy * y + k1.cy;
+        reason[i] = kSim3Image;
         if (!(u >= dst.min_x && u < dst.max_x && v >= dst.min_y && v < dst.max_y)) continue;  // IsInImage
+        reason[i] = kSim3Distance;
         const float maxDistance = 1.2f * src.mp_dmax[i];  // GetMaxDistanceInvariance (MapPoint.cpp:361-365)
         const float minDistance = 0.8f * src.mp_dmin[i];  // GetMinDistanceInvariance (:355-359)
         const float dist3D = std::sqrt((pd[0] * pd[0] + pd[1] * pd[1]) + pd[2] * pd[2]);
         if (dist3D < minDistance || dist3D > maxDistance) continue;
+        reason[i] = kSim3NoCandidate;
         const int level = predict_scale(src.mp_dmax[i], dist3D, dst.log_scale_factor, dst.n_levels);
         const float radius = th * dst.scale_factors[level];
         const std::vector<int> cand = features_in_area(dst, u, v, radius);
@@ -79,7 +86,12 @@ void search_direction(const Sim3KF& src, const Sim3KF& dst, const float* Rsd, co
                 bestIdx = j;
             }
         }
-        if (bestDist <= kThHigh) match[i] = bestIdx;
+        if (bestIdx < 0) continue;  // no keypoint of the octave window in the area
+        reason[i] = kSim3AboveThHigh;
+        if (bestDist <= kThHigh) {
+            match[i] = bestIdx;
+            reason[i] = kSim3Matched;
+        }
     }
 }
 }  // namespace
@@ -94,6 +106,13 @@ int predict_scale(float dmax, float current_dist, float log_scale_factor, int n_
 
 int search_by_sim3(const Sim3KF& k1, const Sim3KF& k2, const int32_t* matched12, const float* R12, const float* t12,
                    float th, int32_t* out12) {
+    std::vector<int32_t> m1(std::max(k1.n, 1)), m2(std::max(k2.n, 1)), r1(m1.size()), r2(m2.size());
+    return search_by_sim3_trace(k1, k2, matched12, R12, t12, th, out12, m1.data(), m2.data(), r1.data(), r2.data());
+}
+
+int search_by_sim3_trace(const Sim3KF& k1, const Sim3KF& k2, const int32_t* matched12, const float* R12,
+                         const float* t12, float th, int32_t* out12, int32_t* m1, int32_t* m2, int32_t* reason1,
+                         int32_t* reason2) {
     // R21 = R12^T, t21 = -R21 * t12 (:963-964)
     float R21[9], t21[3];
     for (int r = 0; r < 3; ++r)
@@ -106,9 +125,9 @@ int search_by_sim3(const Sim3KF& k1, const Sim3KF& k2, const int32_t* matched12,
         const int idx2 = matched12[i];
         if (idx2 >= 0 && idx2 < k2.n) already2[idx2] = 1;
     }
-    std::vector<int> m1(k1.n, -1), m2(k2.n, -1);  // vnMatch1, vnMatch2 (:986-987)
-    search_direction(k1, k2, R21, t21, already1, k1, th, m1);
-    search_direction(k2, k1, R12, t12, already2, k1, th, m2);
+    // m1 = vnMatch1, m2 = vnMatch2 (:986-987)
+    search_direction(k1, k2, R21, t21, already1, k1, th, m1, reason1);
+    search_direction(k2, k1, R12, t12, already2, k1, th, m2, reason2);
     int nFound = 0;  // check agreement (:1152-1167)
     for (int i = 0; i < k1.n; ++i) {
         out12[i] = -1;

@@ -52,6 +52,23 @@ constexpr int kGridCols = 64, kGridRows = 48;  // FRAME_GRID_COLS / ROWS (Frame.
 int search_by_sim3(const Sim3KF& kf1, const Sim3KF& kf2, const int32_t* matched12, const float* R12,
                    const float* t12, float th, int32_t* out12);
 
+// Why a source slot ended as it did, in the order the reference tests (one code per slot and direction).
+enum Sim3Reason : int32_t {
+    kSim3NotSearched = 0,  // NULL, vbAlreadyMatched or isBad (:998-1002, :1078-1082)
+    kSim3Depth = 1,        // z < 0 in the destination camera (:1008, :1088)
+    kSim3Image = 2,        // !IsInImage (:1019, :1099)
+    kSim3Distance = 3,     // outside [minDistance, maxDistance] (:1026, :1106)
+    kSim3NoCandidate = 4,  // GetFeaturesInArea empty, or no keypoint of octave [level - 1, level] in it
+    kSim3AboveThHigh = 5,  // bestDist > TH_HIGH (:1064, :1144)
+    kSim3Matched = 6,      // vnMatch[i] = bestIdx
+};
+
+// search_by_sim3 that also writes both directions: m1[k1.n] = vnMatch1, m2[k2.n] = vnMatch2 (the
+// destination keypoint index or -1) and reason1 / reason2, a Sim3Reason per source slot.
+int search_by_sim3_trace(const Sim3KF& kf1, const Sim3KF& kf2, const int32_t* matched12, const float* R12,
+                         const float* t12, float th, int32_t* out12, int32_t* m1, int32_t* m2, int32_t* reason1,
+                         int32_t* reason2);
+
 // MapPoint::PredictScale (MapPoint.cpp:367-381)
 int predict_scale(float dmax, float current_dist, float log_scale_factor, int n_levels);
 

@@ -207,6 +207,10 @@ struct rsc_context {
     // SearchBySim3: packed KeyFrames + pair table + scratch + outputs (device, pinned mirror)
     DevBuf<char> d_s3m;
     PinBuf<char> h_s3m;
+    // where the last rsc_search_by_sim3_many left each pair's vnMatch1 / vnMatch2 in d_s3m
+    // (rsc_diag_sim3match_directions); empty before the first call and after a failed one
+    struct S3mPair { size_t o_m1, o_m2; int n1, n2; };
+    std::vector<S3mPair> s3m_last;
     // SearchByBoW: pair table + output vectors + match counts (device, pinned mirror)
     DevBuf<char> d_bow;
     PinBuf<char> h_bow;
@@ -2530,6 +2534,13 @@ int check_sim3_kf(const rsc_sim3_kf& k) {
             g_last_error = "mGrid index out of range";
             return RSC_ERR_ARG;
         }
+    // PredictScale converts ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) to int: out of int's range
+    // (undefined) for a non-finite distance bound, so a good MapPoint must carry finite ones
+    for (int i = 0; i < k.n; ++i)
+        if (k.mp_state[i] == 1 && !(std::isfinite(k.mp_dmax[i]) && std::isfinite(k.mp_dmin[i]))) {
+            g_last_error = "non-finite mfMaxDistance / mfMinDistance of a good MapPoint";
+            return RSC_ERR_ARG;
+        }
     return 0;
 }
 }  // namespace
@@ -2544,6 +2555,7 @@ struct rsc_kfview {
     std::vector<int32_t> octave;
     std::vector<uint8_t> mp_state;
     float R[9], t[3], K[4];
+    float top_scale = 1.0f;  // mvScaleFactors[n_levels - 1] (the largest search radius is th times it)
     DevSim3KF dev;           // the header as uploaded (device pointers), for SearchByProjection's problem table
     DevBuf<float> d_angle;   // mvKeysUn[i].angle (rsc_kfview_set_angles)
     bool has_angles = false;
@@ -2607,6 +2619,7 @@ int rsc_kfview_create(rsc_context* C, const rsc_sim3_kf* k, rsc_kfview** out) {
     std::memcpy(v->R, k->Rcw, sizeof(v->R));
     std::memcpy(v->t, k->tcw, sizeof(v->t));
     v->K[0] = k->fx; v->K[1] = k->fy; v->K[2] = k->cx; v->K[3] = k->cy;
+    v->top_scale = k->scale_factors[k->n_levels - 1];
     *out = v.release();
     return RSC_OK;
 }
@@ -2621,10 +2634,19 @@ int rsc_search_by_sim3_many(rsc_context* C, rsc_kfview* const* kf1, rsc_kfview* 
                             const float* R12, const float* t12, float th, const int32_t* const* matched12,
                             int32_t* const* out12, int32_t* nfound) {
     if (!C || count < 0 || (count && (!kf1 || !kf2 || !R12 || !t12 || !matched12 || !out12))) return RSC_ERR_ARG;
+    C->s3m_last.clear();
     if (count == 0) return RSC_OK;
+    // GetFeaturesInArea converts (u - mnMinX + r) * mfGridElementWidthInv to int, undefined out of int's
+    // range: the u term is below 64 cells, so the radius term is kept below 2^30 cells (rsc.h)
+    if (!std::isfinite(th)) return RSC_ERR_ARG;
     int max_points = 0;
     for (int c = 0; c < count; ++c) {
         if (!kf1[c] || !kf2[c] || kf1[c]->ctx != C || kf2[c]->ctx != C) return RSC_ERR_ARG;
+        for (const rsc_kfview* v : {kf1[c], kf2[c]})
+            if (!(th * v->top_scale * std::max(v->dev.gw_inv, v->dev.gh_inv) < 1073741824.0f)) {
+                g_last_error = "SearchBySim3 radius out of the grid arithmetic's range";
+                return RSC_ERR_ARG;
+            }
         if (kf1[c]->n && (!matched12[c] || !out12[c])) return RSC_ERR_ARG;
         max_points = std::max(max_points, std::max(kf1[c]->n, kf2[c]->n));
     }
@@ -2695,6 +2717,19 @@ int rsc_search_by_sim3_many(rsc_context* C, rsc_kfview* const* kf1, rsc_kfview* 
         if (kf1[c]->n) std::memcpy(out12[c], h + o_out[c], 4 * (size_t)kf1[c]->n);
         if (nfound) std::memcpy(&nfound[c], h + o_nf[c], 4);
     }
+    C->s3m_last.resize((size_t)count);
+    for (int c = 0; c < count; ++c) C->s3m_last[c] = {o_m1[c], o_m2[c], kf1[c]->n, kf2[c]->n};
+    return RSC_OK;
+}
+
+int rsc_diag_sim3match_directions(rsc_context* C, int pair, int32_t* m1, int n1, int32_t* m2, int n2) {
+    if (!C || pair < 0 || (size_t)pair >= C->s3m_last.size()) return RSC_ERR_ARG;
+    const auto& p = C->s3m_last[(size_t)pair];
+    if (n1 != p.n1 || n2 != p.n2 || (n1 && !m1) || (n2 && !m2)) return RSC_ERR_ARG;
+    RSC_HIP(hipSetDevice(C->device));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    if (n1) RSC_HIP(hipMemcpy(m1, C->d_s3m.p + p.o_m1, 4 * (size_t)n1, hipMemcpyDeviceToHost));
+    if (n2) RSC_HIP(hipMemcpy(m2, C->d_s3m.p + p.o_m2, 4 * (size_t)n2, hipMemcpyDeviceToHost));
     return RSC_OK;
 }
 

@@ -45,7 +45,7 @@ EXPORTED = [
     "rsc_reloc_events", "rsc_loop_events", "rsc_pose_optimization_many",
     "rsc_bow_create", "rsc_bow_destroy", "rsc_bow_set_valid", "rsc_search_by_bow_frame_many",
     "rsc_search_by_bow_kf_many", "rsc_diag_bow_phase_stamps", "rsc_diag_refine_phase_stamps", "rsc_diag_solve_phase_stamps", "rsc_diag_poseopt_phases", "rsc_diag_sim3opt_phases", "rsc_diag_kfdb_stamps",
-    "rsc_search_by_sim3_many", "rsc_kfview_create", "rsc_kfview_destroy",
+    "rsc_search_by_sim3_many", "rsc_diag_sim3match_directions", "rsc_kfview_create", "rsc_kfview_destroy",
     "rsc_optimize_sim3_many",
     "rsc_kfdb_create", "rsc_kfdb_destroy", "rsc_kfdb_add", "rsc_kfdb_erase", "rsc_kfdb_release", "rsc_kfdb_clear",
     "rsc_kfdb_set_covisibility", "rsc_kfdb_set_covisibility_many", "rsc_kfdb_detect_relocalization", "rsc_kfdb_detect_loop", "rsc_kfdb_state",
@@ -189,9 +189,10 @@ class Sim3KFStruct(C.Structure):
 def sim3_kf_struct(kf):
     """(ctypes rsc_sim3_kf, keep-alive arrays) for a rsc.synth.Sim3KF-like object."""
     from rsc import synth
+    sf, log_sf, gw_inv, gh_inv = synth.kf_geometry(kf)  # the KeyFrame's own, else the synth constants
     keep = [np.ascontiguousarray(kf.kp, np.float32), np.ascontiguousarray(kf.octave, np.int32),
             np.ascontiguousarray(kf.desc, np.uint8), np.ascontiguousarray(kf.cell_begin, np.int32),
-            np.ascontiguousarray(kf.cell_feat, np.int32), synth.scale_factors(),
+            np.ascontiguousarray(kf.cell_feat, np.int32), sf,
             np.ascontiguousarray(kf.mp_state, np.uint8), np.ascontiguousarray(kf.mp_pos, np.float32),
             np.ascontiguousarray(kf.mp_dmax, np.float32), np.ascontiguousarray(kf.mp_dmin, np.float32),
             np.ascontiguousarray(kf.mp_desc, np.uint8)]
@@ -202,10 +203,10 @@ def sim3_kf_struct(kf):
     (k.kp, k.octave, k.desc, k.cell_begin, k.cell_feat, k.scale_factors, k.mp_state, k.mp_pos, k.mp_dmax,
      k.mp_dmin, k.mp_desc) = (a.ctypes.data for a in keep)
     k.min_x, k.max_x, k.min_y, k.max_y = kf.min_x, kf.max_x, kf.min_y, kf.max_y
-    k.grid_w_inv, k.grid_h_inv = float(synth.GRID_W_INV), float(synth.GRID_H_INV)
+    k.grid_w_inv, k.grid_h_inv = float(gw_inv), float(gh_inv)
     k.fx, k.fy, k.cx, k.cy = kf.fx, kf.fy, kf.cx, kf.cy
     k.n_levels = len(keep[5])
-    k.log_scale_factor = float(synth.LOG_SCALE_FACTOR)
+    k.log_scale_factor = float(log_sf)
     k.Rcw[:] = [float(v) for v in np.asarray(kf.Rcw, np.float32).reshape(9)]
     k.tcw[:] = [float(v) for v in np.asarray(kf.tcw, np.float32).reshape(3)]
     return k, keep
@@ -497,12 +498,23 @@ class Sim3Search:
         self.pout = (C.c_void_p * max(c, 1))(*[a.ctypes.data for a in self.out])
         self.nfound = np.zeros(max(c, 1), np.int32)
         self.n1 = [p[0].n for p in problems]
+        self.n2 = [p[1].n for p in problems]
 
     def run(self):
         _check(load_library().rsc_search_by_sim3_many(self.ctx.h, self.h1, self.h2, self.count, self.R, self.t,
                                                       self.th, self.pin, self.pout, self.nfound),
                "rsc_search_by_sim3_many")
         return [o[:n] for o, n in zip(self.out, self.n1)], self.nfound[:self.count]
+
+    def directions(self, k: int):
+        """(m1 int32[kf1.n] = vnMatch1, m2 int32[kf2.n] = vnMatch2) of pair k as the context's most recent
+        SearchBySim3 call left them, before the agreement step (rsc_diag_sim3match_directions)."""
+        n1 = self.n1[k] if 0 <= k < self.count else 0
+        n2 = self.n2[k] if 0 <= k < self.count else 0
+        m1, m2 = np.full(max(n1, 1), -7, np.int32), np.full(max(n2, 1), -7, np.int32)
+        _check(load_library().rsc_diag_sim3match_directions(self.ctx.h, int(k), m1, n1, m2, n2),
+               "rsc_diag_sim3match_directions")
+        return m1[:n1], m2[:n2]
 
 
 def search_by_sim3_many(ctx: Context, problems, th: float = 7.5):
@@ -733,6 +745,7 @@ def load_library(path: str = LIB_PATH):
     L.rsc_kfview_destroy.argtypes = [vp]
     L.rsc_search_by_sim3_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_, f32p_, C.c_float,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i32p]
+    L.rsc_diag_sim3match_directions.argtypes = [vp, C.c_int, i32p, C.c_int, i32p, C.c_int]
     u32p_ = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
     f64p_ = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     u64p_ = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")

@@ -457,6 +457,11 @@ class Sim3KF:
     max_x: float = float(WIDTH)
     min_y: float = 0.0
     max_y: float = float(HEIGHT)
+    # per-KeyFrame pyramid and grid geometry; None = the module constants below
+    scale_factors: np.ndarray = None   # float32 [n_levels] mvScaleFactors
+    log_scale_factor: float = None     # mfLogScaleFactor
+    grid_w_inv: float = None           # mfGridElementWidthInv
+    grid_h_inv: float = None           # mfGridElementHeightInv
 
 
 def scale_factors() -> np.ndarray:
@@ -471,10 +476,31 @@ GRID_W_INV = np.float32(np.float32(GRID_COLS) / np.float32(WIDTH))   # mfGridEle
 GRID_H_INV = np.float32(np.float32(GRID_ROWS) / np.float32(HEIGHT))
 
 
-def build_grid(kp: np.ndarray):
-    """Frame::AssignFeaturesToGrid (PosInGrid with round()), as CSR over cell = ix * 48 + iy."""
-    px = np.floor((kp[:, 0] - 0.0) * GRID_W_INV + 0.5).astype(np.int64)
-    py = np.floor((kp[:, 1] - 0.0) * GRID_H_INV + 0.5).astype(np.int64)
+def kf_geometry(kf):
+    """(scale_factors float32[n_levels], log_scale_factor, grid_w_inv, grid_h_inv) of a Sim3KF-like object:
+    its own values, the module constants where it carries none."""
+    def own(name, default):
+        v = getattr(kf, name, None)
+        return default if v is None else v
+    return (np.ascontiguousarray(own("scale_factors", scale_factors()), np.float32),
+            np.float32(own("log_scale_factor", LOG_SCALE_FACTOR)), np.float32(own("grid_w_inv", GRID_W_INV)),
+            np.float32(own("grid_h_inv", GRID_H_INV)))
+
+
+def _c_round(a: np.ndarray) -> np.ndarray:
+    """C round() of float32 values: halves away from zero (np.round rounds them to even)."""
+    a = np.asarray(a, np.float32).astype(np.float64)
+    return (np.sign(a) * np.floor(np.abs(a) + 0.5)).astype(np.int64)
+
+
+def build_grid(kp: np.ndarray, min_x: float = 0.0, min_y: float = 0.0, grid_w_inv=None, grid_h_inv=None):
+    """Frame::AssignFeaturesToGrid, as CSR over cell = ix * 48 + iy; the cell of a keypoint is
+    PosInGrid's round((x - mnMinX) * mfGridElementWidthInv) in float."""
+    kp = np.asarray(kp, np.float32).reshape(-1, 2)
+    gw = np.float32(GRID_W_INV if grid_w_inv is None else grid_w_inv)
+    gh = np.float32(GRID_H_INV if grid_h_inv is None else grid_h_inv)
+    px = _c_round((kp[:, 0] - np.float32(min_x)) * gw)
+    py = _c_round((kp[:, 1] - np.float32(min_y)) * gh)
     ok = (px >= 0) & (px < GRID_COLS) & (py >= 0) & (py < GRID_ROWS)
     cell = np.where(ok, px * GRID_ROWS + py, -1)
     idx = np.nonzero(ok)[0]

@@ -146,6 +146,7 @@ def lib():
                                          C.c_int64, i32p]
     L.ora_descriptor_distance.argtypes = [u8p, u8p]
     L.ora_search_by_sim3.argtypes = [vp, vp, i32p, f32p, f32p, C.c_float, i32p]
+    L.ora_search_by_sim3_trace.argtypes = [vp, vp, i32p, f32p, f32p, C.c_float, i32p, i32p, i32p, i32p, i32p]
     L.ora_predict_scale.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int]
     u32p_ = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
     f64p_ = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -526,6 +527,22 @@ def search_by_sim3(kf1, kf2, R12, t12, matched12, th=7.5):
                                   np.ascontiguousarray(np.asarray(R12, np.float32).reshape(9)),
                                   np.ascontiguousarray(np.asarray(t12, np.float32).reshape(3)), th, out)
     return nf, out[:kf1.n]
+
+
+def search_by_sim3_trace(kf1, kf2, R12, t12, matched12, th=7.5):
+    """search_by_sim3 with both directions: (nfound, out12, m1 int32[kf1.n] = vnMatch1, m2 int32[kf2.n] =
+    vnMatch2, reason1, reason2 = a Sim3Reason code (oracle/sim3match_oracle.h) per source slot)."""
+    from rsc import engine
+    k1, keep1 = engine.sim3_kf_struct(kf1)
+    k2, keep2 = engine.sim3_kf_struct(kf2)
+    a1 = [np.full(max(kf1.n, 1), -7, np.int32) for _ in range(3)]
+    a2 = [np.full(max(kf2.n, 1), -7, np.int32) for _ in range(2)]
+    m12 = np.ascontiguousarray(matched12, np.int32)
+    nf = lib().ora_search_by_sim3_trace(C.addressof(k1), C.addressof(k2), m12 if m12.size else np.zeros(1, np.int32),
+                                        np.ascontiguousarray(np.asarray(R12, np.float32).reshape(9)),
+                                        np.ascontiguousarray(np.asarray(t12, np.float32).reshape(3)), th,
+                                        a1[0], a1[1], a2[0], a1[2], a2[1])
+    return nf, a1[0][:kf1.n], a1[1][:kf1.n], a2[0][:kf2.n], a1[2][:kf1.n], a2[1][:kf2.n]
 
 
 class OracleKFDB:

@@ -5,9 +5,12 @@
 * hand-built known answers (ORBmatcher.cpp:948-1170): the mutual-agreement rule, already-matched
   (with and without an index in KF2) and bad MapPoints, the octave window [level-1, level],
   TH_HIGH inclusive;
-* an independent pure-Python restatement (numpy float32 scalars) against the C oracle on random
-  pairs — the branches not hand-built above (depth, IsInImage, scale-invariance window, grid-order
-  first minimum, pKF1's intrinsics in both directions) are exercised there;
+* an independent pure-Python restatement (sim3match_ref.py, numpy float32 scalars) against the C
+  oracle on random pairs: these reach the depth, IsInImage and scale-invariance branches, but both
+  KeyFrames of a random pair share intrinsics, bounds and pyramid and KF1 sits at the origin, so
+  "pKF1's intrinsics in both directions", source/destination mix-ups, exact boundaries and tie order
+  are NOT exercised here — test_cpu_sim3match_cases.py does that on hand-built cases and pins which
+  mistakes the random pairs miss;
 * the committed golden fixture tests/golden/sim3match_traces.npz.
 
 The reference ships no tests for this path; the known answers follow its text.
@@ -20,6 +23,7 @@ import pytest
 
 import oracle_lib as ol
 from rsc import synth
+from sim3match_ref import py_search
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -54,82 +58,6 @@ def test_predict_scale(dmax, dist, expect):
         q = f32(np.float32(ol.lib().ora_dm_log(float(r))) / synth.LOG_SCALE_FACTOR)
         expect = int(math.ceil(q))
     assert got == expect
-
-
-# ---- independent restatement (pure Python + numpy float32 scalars) ----------------------------
-def py_search(kf1, kf2, R12, t12, m12, th=7.5):
-    L = ol.lib()
-    sf = synth.scale_factors()
-    R12 = np.asarray(R12, f32).reshape(3, 3)
-    t12 = np.asarray(t12, f32).reshape(3)
-    R21 = R12.T.copy()
-    t21 = np.array([-f32(f32(f32(R21[r, 0] * t12[0]) + f32(R21[r, 1] * t12[1])) + f32(R21[r, 2] * t12[2]))
-                    for r in range(3)], f32)
-
-    def rot_add(R, x, t):
-        R = np.asarray(R, f32).reshape(3, 3)
-        return np.array([f32(f32(f32(f32(R[r, 0] * x[0]) + f32(R[r, 1] * x[1])) + f32(R[r, 2] * x[2])) + t[r])
-                         for r in range(3)], f32)
-
-    def direction(src, dst, Rsd, tsd, already):
-        out = [-1] * src.n
-        for i in range(src.n):
-            if src.mp_state[i] != 1 or already[i]:
-                continue
-            pc = rot_add(src.Rcw, src.mp_pos[i], np.asarray(src.tcw, f32))
-            pd = rot_add(Rsd, pc, tsd)
-            if pd[2] < 0:
-                continue
-            invz = f32(1.0 / np.float64(pd[2]))
-            x, y = f32(pd[0] * invz), f32(pd[1] * invz)
-            u = f32(f32(f32(kf1.fx) * x) + f32(kf1.cx))
-            v = f32(f32(f32(kf1.fy) * y) + f32(kf1.cy))
-            if not (u >= dst.min_x and u < dst.max_x and v >= dst.min_y and v < dst.max_y):
-                continue
-            mx, mn = f32(f32(1.2) * src.mp_dmax[i]), f32(f32(0.8) * src.mp_dmin[i])
-            d3 = np.sqrt(f32(f32(f32(pd[0] * pd[0]) + f32(pd[1] * pd[1])) + f32(pd[2] * pd[2])))
-            if d3 < mn or d3 > mx:
-                continue
-            ratio = f32(src.mp_dmax[i] / d3)
-            lvl = int(math.ceil(f32(np.float32(L.ora_dm_log(float(ratio))) / synth.LOG_SCALE_FACTOR)))
-            lvl = min(max(lvl, 0), len(sf) - 1)
-            r = f32(f32(th) * sf[lvl])
-            gx, gy = synth.GRID_W_INV, synth.GRID_H_INV
-            x0 = max(0, math.floor(f32(f32(f32(u - f32(dst.min_x)) - r) * gx)))
-            x1 = min(63, math.ceil(f32(f32(f32(u - f32(dst.min_x)) + r) * gx)))
-            y0 = max(0, math.floor(f32(f32(f32(v - f32(dst.min_y)) - r) * gy)))
-            y1 = min(47, math.ceil(f32(f32(f32(v - f32(dst.min_y)) + r) * gy)))
-            if x0 >= 64 or x1 < 0 or y0 >= 48 or y1 < 0:
-                continue
-            best, bi = 1 << 31, -1
-            for ix in range(x0, x1 + 1):
-                for iy in range(y0, y1 + 1):
-                    c = ix * 48 + iy
-                    for e in range(dst.cell_begin[c], dst.cell_begin[c + 1]):
-                        j = int(dst.cell_feat[e])
-                        if not (abs(f32(dst.kp[j, 0] - u)) < r and abs(f32(dst.kp[j, 1] - v)) < r):
-                            continue
-                        if dst.octave[j] < lvl - 1 or dst.octave[j] > lvl:
-                            continue
-                        d = int(np.unpackbits(np.bitwise_xor(src.mp_desc[i], dst.desc[j])).sum())
-                        if d < best:
-                            best, bi = d, j
-            if best <= 100:
-                out[i] = bi
-        return out
-
-    a1 = [m != -1 for m in m12]
-    a2 = [False] * kf2.n
-    for m in m12:
-        if m >= 0:
-            a2[m] = True
-    m1 = direction(kf1, kf2, R21, t21, a1)
-    m2 = direction(kf2, kf1, R12, t12, a2)
-    out = np.full(kf1.n, -1, np.int32)
-    for i in range(kf1.n):
-        if m1[i] >= 0 and m2[m1[i]] == i:
-            out[i] = m1[i]
-    return int((out >= 0).sum()), out
 
 
 def test_random_pairs_match_python_restatement():

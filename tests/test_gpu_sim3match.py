@@ -15,10 +15,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def check(problems, th=7.5):
-    outs, nf = engine.search_by_sim3_many(ctx(), problems, th)
-    for (kf1, kf2, R12, t12, m12), o, n in zip(problems, outs, nf):
+    s = engine.Sim3Search(ctx(), problems, th)
+    outs, nf = s.run()
+    for k, ((kf1, kf2, R12, t12, m12), o, n) in enumerate(zip(problems, outs, nf)):
         on, oo = ol.search_by_sim3(kf1, kf2, R12, t12, m12, th)
         assert n == on and np.array_equal(o, oo)
+        # both directions before the agreement step, which hides most one-directional errors
+        tn, to, om1, om2, _, _ = ol.search_by_sim3_trace(kf1, kf2, R12, t12, m12, th)
+        m1, m2 = s.directions(k)
+        assert tn == on and np.array_equal(to, oo) and np.array_equal(m1, om1) and np.array_equal(m2, om2)
     return nf
 
 
