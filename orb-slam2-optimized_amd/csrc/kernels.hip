@@ -105,11 +105,10 @@ __global__ __launch_bounds__(64) void pnp_betas_kernel(const DevPnP* __restrict_
                                                        const int2* __restrict__ wg_table, int ngroups,
                                                        const double* __restrict__ stage,
                                                        const int32_t* __restrict__ samples,
-                                                       float* __restrict__ poses, double* __restrict__ berr,
-                                                       float* __restrict__ bpose, unsigned* __restrict__ bctr,
+                                                       double* __restrict__ berr, float* __restrict__ bpose,
                                                        size_t hcap, int hb) {
     __shared__ __attribute__((aligned(16))) double smem[kBetasWaveSmemDoubles];
-    pnp_betas_wave_body<NS>(probs, lps, wg_table, ngroups, hb, stage, samples, poses, berr, bpose, bctr, hcap, smem);
+    pnp_betas_wave_body<NS>(probs, lps, wg_table, ngroups, hb, stage, samples, berr, bpose, hcap, smem);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -150,7 +149,9 @@ template <int PPT>
 __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict__ probs,
                                                        const LaunchProb* __restrict__ lps,
                                                        const int4* __restrict__ wg_table,  // lp, hyp0, count
-                                                       const float* __restrict__ poses,
+                                                       const double* __restrict__ berr,
+                                                       const float* __restrict__ bpose, size_t hcap,
+                                                       float* __restrict__ poses,
                                                        int32_t* __restrict__ counts,
                                                        int32_t* __restrict__ counts_dev,
                                                        uint64_t* __restrict__ masks, int mask_words,
@@ -168,6 +169,18 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
     const LaunchProb& lp = lps[wt.x];
     const DevPnP& P = probs[lp.prob];
     const double fx = P.fx, fy = P.fy, cx = P.cx, cy = P.cy;
+    // The hypothesis' pose is the betas stage's approximation with the smallest error, in the
+    // reference's order (PnPsolver.cpp:393-414: 1, then 2 if smaller, then 3 if smaller; a NaN never
+    // wins over an earlier value).  Lane l takes the chunk's hypothesis l (a chunk holds at most 64,
+    // rsc_api.cpp pnp_scan_partition / scan_chunk): the choices of the whole chunk are two wave
+    // masks in scalar registers, so the loop below finds each pose with scalar shifts alone.
+    const size_t rec0 = (size_t)(lp.out0 + wt.y);
+    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
+    if (lane < wt.z) {
+        e0 = berr[rec0 + lane];
+        e1 = berr[hcap + rec0 + lane];
+        e2 = berr[2 * hcap + rec0 + lane];
+    }
     float X[PPT], Y[PPT], Z[PPT], U[PPT], V[PPT], E[PPT];
     RSC_UNROLL for (int s = 0; s < PPT; ++s) {
         const int i = s * 256 + tid;
@@ -179,11 +192,28 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
             X[s] = 0.f; Y[s] = 0.f; Z[s] = 1.f; E[s] = -1.f; U[s] = 0.f; V[s] = 0.f;  // never an inlier
         }
     }
+    int best = 0;
+    {
+        double be = e0;
+        if (e1 < be) { be = e1; best = 1; }
+        if (e2 < be) { be = e2; best = 2; }
+    }
+    const uint64_t pick1 = __ballot(best == 1), pick2 = __ballot(best == 2);
+    auto pose_of = [&](int j) {  // hypothesis j of the chunk: its selected record in bpose
+        const size_t apx = (size_t)((pick1 >> j) & 1u) + 2 * (size_t)((pick2 >> j) & 1u);
+        return bpose + (apx * hcap + rec0 + (size_t)j) * 12;
+    };
+    // the selected poses go to `poses` (the select / refine kernels, the gather and the parity
+    // hooks read them there): every hypothesis belongs to exactly one scan workgroup
+    for (int w = tid; w < wt.z * 12; w += 256) {
+        const int hj = w / 12, k = w - 12 * hj;
+        poses[(rec0 + hj) * 12 + k] = pose_of(hj)[k];
+    }
     // The PPT points of a lane are independent: all ballots are taken first and the mask words
     // are kept by lanes 0..PPT-1 in one predicated store, so the compiler can interleave the
     // points' arithmetic (a lane-0 branch per point would serialise them).  The next pose is
     // loaded before the current one is used.
-    const float* pp = poses + (size_t)(lp.out0 + wt.y) * 12;
+    const float* pp = pose_of(0);
     float Rn[9], tn[3];
     RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
     RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
@@ -192,7 +222,7 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
         RSC_UNROLL for (int k = 0; k < 9; ++k) R[k] = Rn[k];
         RSC_UNROLL for (int k = 0; k < 3; ++k) t[k] = tn[k];
         if (j + 1 < wt.z) {
-            pp += 12;
+            pp = pose_of(j + 1);
             RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
             RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
         }
@@ -1125,7 +1155,7 @@ static hipError_t launch_eig_rows(int nwgE, const int2* wgtE, const DevPnP* prob
 
 hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, const int2* wgtB,
                                   const DevPnP* probs, const LaunchProb* lps, const uint32_t* T, double* stage,
-                                  float* poses, int32_t* samples, const BetasScratch& bs, hipStream_t st,
+                                  int32_t* samples, const BetasScratch& bs, hipStream_t st,
                                   hipEvent_t eig_begin, hipEvent_t eig_end, bool eig_rows, bool eig_split,
                                   unsigned* fault, int betas_hb) {
     if (ns < 4 || ns > 6 || betas_hb < 1 || betas_hb > kBetasHyps) return hipErrorInvalidValue;
@@ -1143,8 +1173,8 @@ hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, 
         else                                                                                          \
             pnp_eig_group_kernel<N><<<nwgE, 64, 0, st>>>(probs, lps, wgtE, T, stage, samples);        \
         if (eig_end) (void)hipEventRecord(eig_end, st);                                               \
-        pnp_betas_kernel<N><<<3 * nwgB, 64, 0, st>>>(probs, lps, wgtB, nwgB, stage, samples, poses,   \
-                                                     bs.err, bs.pose, bs.ctr, bs.hcap, betas_hb);     \
+        pnp_betas_kernel<N><<<3 * nwgB, 64, 0, st>>>(probs, lps, wgtB, nwgB, stage, samples,          \
+                                                     bs.err, bs.pose, bs.hcap, betas_hb);             \
         break;
         RSC_CASE(4) RSC_CASE(5) RSC_CASE(6)
 #undef RSC_CASE
@@ -1277,15 +1307,24 @@ hipError_t launch_selftest_math(int fn, const double* x, int n, double* out, hip
 }
 
 hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const int4* wgt,
-                           const float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks, int mask_words,
-                           int32_t* qual, hipStream_t st) {
+                           const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks,
+                           int mask_words, int32_t* qual, hipStream_t st) {
     switch (ppt) {
-#define RSC_CASE(P) case P: pnp_scan_kernel<P><<<nwg, 256, 0, st>>>(probs, lps, wgt, poses, counts, counts_dev, masks, mask_words, qual); break;
+#define RSC_CASE(P) case P: pnp_scan_kernel<P><<<nwg, 256, 0, st>>>(probs, lps, wgt, bs.err, bs.pose, bs.hcap, poses, counts, counts_dev, masks, mask_words, qual); break;
         RSC_CASE(1) RSC_CASE(2) RSC_CASE(4) RSC_CASE(8) RSC_CASE(16) RSC_CASE(32)
 #undef RSC_CASE
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t pnp_scan_occupancy(int ppt, int* wgs_per_cu) {
+    switch (ppt) {
+#define RSC_CASE(P) case P: return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, reinterpret_cast<const void*>(&pnp_scan_kernel<P>), 256, 0);
+        RSC_CASE(1) RSC_CASE(2) RSC_CASE(4) RSC_CASE(8) RSC_CASE(16) RSC_CASE(32)
+#undef RSC_CASE
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t read_solve_stamps(uint64_t* out) {

@@ -150,6 +150,52 @@ int scan_chunk(int total_hyps) {
     while (hc > 8 && (total_hyps + hc - 1) / hc < target) hc >>= 1;
     return hc;
 }
+// The PnP rounds size their scan from the device's capacity (pnp_scan_partition) unless the
+// variable is set: then they too use scan_chunk's power-of-two chunks with a remainder chunk.
+bool scan_wgs_overridden() {
+    static const bool set = std::getenv("RSC_SCAN_WGS") != nullptr;
+    return set;
+}
+
+// Scan workgroups of a PnP round: chunks[i] even chunks for problem i's H[i] hypotheses (sizes
+// differ by at most one, even_chunk below).  `capacity` is what the device holds at once
+// (pnp_scan_kernel<PPT>'s workgroups per CU x CUs) and `batch` the kernel's mask batch B.
+//   * The round gets k x capacity workgroups, dealt to the problems in proportion to their
+//     hypotheses, with the smallest k whose chunks fit one mask batch: whole rounds of residency, so
+//     no CU idles through a part-filled last round, and each workgroup's head (table -> launch
+//     record -> problem -> points) is paid for as many hypotheses as a full device allows
+//     (config 2: 1,280 x 15 instead of 2,432 x 8 or 4).
+//   * Never fewer than kScanMinChunk hypotheses per point load, so a round too small to fill the
+//     device (the single event) keeps ceil(H / 8) workgroups per problem: it is latency-bound and
+//     wants the width.
+// Placement only: the counts, masks and poses do not depend on it.
+constexpr int kScanMinChunk = 8;
+void pnp_scan_partition(const int* H, int count, int capacity, int batch, std::vector<int>& chunks) {
+    chunks.assign((size_t)count, 1);
+    int64_t total = 0;
+    for (int i = 0; i < count; ++i) total += H[i];
+    if (total <= 0) return;
+    capacity = std::max(capacity, 1);
+    batch = std::max(batch, kScanMinChunk);
+    const int kmax = (int)(total / capacity) + 1;  // k x capacity > total: every share is at its upper bound
+    for (int k = 1; k <= kmax; ++k) {
+        bool fits = true;
+        for (int i = 0; i < count; ++i) {
+            const int h = std::max(H[i], 1);
+            const int lo = (h + batch - 1) / batch, hi = (h + kScanMinChunk - 1) / kScanMinChunk;
+            const int64_t share = (int64_t)k * capacity * h / total;  // floor: the sum stays <= k x capacity
+            if (share < lo && k < kmax) { fits = false; break; }
+            chunks[i] = (int)std::min<int64_t>(std::max<int64_t>(share, lo), hi);
+        }
+        if (fits) break;
+    }
+}
+// Chunk c of n even chunks of H hypotheses: [h0, h0 + len), the first H % n chunks one longer.
+inline void even_chunk(int H, int n, int c, int& h0, int& len) {
+    const int q = H / n, r = H % n;
+    h0 = c * q + std::min(c, r);
+    len = q + (c < r ? 1 : 0);
+}
 
 int ppt_for(int n) {
     int need = (n + 255) / 256;
@@ -175,9 +221,8 @@ struct rsc_context {
     DevBuf<uint64_t> d_masks;
     DevBuf<int32_t> d_samples;
     DevBuf<double> d_stage;  // quad path: per-hypothesis stage records between the two solve kernels
-    DevBuf<double> d_berr;   // pnp_betas_kernel hand-off: error per (approximation, record)
-    DevBuf<float> d_bpose;   //   float pose per (approximation, record)
-    DevBuf<unsigned> d_bctr; //   one arrival counter per 64-hypothesis group (zero between launches)
+    DevBuf<double> d_berr;   // pnp_betas_kernel results for the scan: error per (approximation, record)
+    DevBuf<float> d_bpose;   //   float pose [12] per (approximation, record)
     DevBuf<float> d_gather;  // gathered pose records (+ their indices)
     DevBuf<double> d_mposes; // MLPnP hypothesis poses, double[12] per record
     DevBuf<char> d_desc;
@@ -189,6 +234,9 @@ struct rsc_context {
     DevBuf<char> d_pnp_tab;
     std::vector<int> pnp_tab_key;
     size_t pnp_tab_quad[3] = {0, 0, 0}, pnp_tab_solve[3] = {0, 0, 0}, pnp_tab_scan = 0;
+    // resident pnp_scan_kernel<PPT> workgroups of the device, [log2 PPT] (occupancy query x CU count,
+    // read at the first round that needs it; 0: not read yet)
+    int pnp_scan_capacity[6] = {0, 0, 0, 0, 0, 0};
     PinBuf<float> h_small;
     PinBuf<float> h_pick;  // Sim3 pick records of the last round, [solver][16]
     DevBuf<char> d_refine;
@@ -518,12 +566,31 @@ struct HipPnPBackend : PnPBackend {
         std::vector<int2>* solve_wgs = solve_wgs_tl;
         std::vector<int2>* quad_wgs = quad_wgs_tl;
         std::vector<int4>& scan_wgs = scan_wgs_tl;
-        const int HC = scan_chunk(total);  // hypotheses per scan workgroup
+        // scan workgroups: even chunks sized from the device's capacity (pnp_scan_partition), or
+        // RSC_SCAN_WGS's chunks of HC hypotheses with a remainder chunk
+        const int HC = scan_wgs_overridden() ? scan_chunk(total) : 0;
+        int scan_cap = 0;
+        if (!HC) {
+            int lg = 0;
+            while ((1 << lg) < ppt) ++lg;
+            if (!C->pnp_scan_capacity[lg]) {
+                int per_cu = 0, cus = 0;
+                RSC_HIP(pnp_scan_occupancy(ppt, &per_cu));
+                RSC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, C->device));
+                if (per_cu <= 0 || cus <= 0) {
+                    g_last_error = "pnp_scan_kernel: no resident workgroup (occupancy query)";
+                    return RSC_ERR_INTERNAL;
+                }
+                C->pnp_scan_capacity[lg] = per_cu * cus;
+            }
+            scan_cap = C->pnp_scan_capacity[lg];
+        }
+        const int scan_batch = ppt <= 8 ? 64 : 512 / ppt;  // pnp_scan_kernel's B
         const int hb = (total <= kEigHyps * C->eig_rows_max_wgs) ? C->betas_small_hb : kBetasHyps;
 
-        // The tables depend only on the round's shape (count, sample size and H per problem, HC):
-        // a round with the shape of the previous one on this thread reuses them (building and
-        // XCD-ordering ~3.7k entries costs ~10 us of host time per config-2 round).
+        // The tables depend only on the round's shape (count, sample size and H per problem, the scan's
+        // chunking): a round with the shape of the previous one on this thread reuses them (building
+        // and XCD-ordering ~2.5k entries costs ~10 us of host time per config-2 round).
         thread_local std::vector<int> shape_tl;
         std::vector<int>& shape = shape_tl;
         thread_local std::vector<int> key_tl;
@@ -531,6 +598,8 @@ struct HipPnPBackend : PnPBackend {
         key.clear();
         key.push_back(count);
         key.push_back(HC);
+        key.push_back(scan_cap);
+        key.push_back(scan_batch);
         key.push_back(hb);
         for (int i = 0; i < count; ++i) {
             key.push_back(S[i]->mRansacMinSet);
@@ -539,12 +608,23 @@ struct HipPnPBackend : PnPBackend {
         if (key != shape) {
             for (int g = 0; g < 3; ++g) { solve_wgs[g].clear(); quad_wgs[g].clear(); }
             scan_wgs.clear();
+            thread_local std::vector<int> chunks_tl;
+            std::vector<int>& chunks = chunks_tl;
+            if (!HC) pnp_scan_partition(H, count, scan_cap, scan_batch, chunks);
             for (int i = 0; i < count; ++i) {
                 const int g = S[i]->mRansacMinSet - 4;
                 for (int h0 = 0; h0 < H[i]; h0 += hb) solve_wgs[g].push_back(make_int2(i, h0));
                 for (int h0 = 0; h0 < H[i]; h0 += kEigHyps) quad_wgs[g].push_back(make_int2(i, h0));
-                for (int h0 = 0; h0 < H[i]; h0 += HC)
-                    scan_wgs.push_back(make_int4(i, h0, std::min(HC, H[i] - h0), 0));
+                if (HC) {
+                    for (int h0 = 0; h0 < H[i]; h0 += HC)
+                        scan_wgs.push_back(make_int4(i, h0, std::min(HC, H[i] - h0), 0));
+                } else if (H[i] > 0) {
+                    for (int c = 0; c < chunks[i]; ++c) {
+                        int h0, len;
+                        even_chunk(H[i], chunks[i], c, h0, len);
+                        scan_wgs.push_back(make_int4(i, h0, len, 0));
+                    }
+                }
             }
             for (int g = 0; g < 3; ++g) {
                 xcd_order(solve_wgs[g], [](const int2& w) { return w.x; });
@@ -599,12 +679,7 @@ struct HipPnPBackend : PnPBackend {
         if (int e = C->d_stage.ensure((size_t)total * kStageDoubles)) return e;
         if (int e = C->d_berr.ensure((size_t)total * 3)) return e;
         if (int e = C->d_bpose.ensure((size_t)total * 36)) return e;
-        size_t groups = 0;
-        for (int g = 0; g < 3; ++g) groups = std::max(groups, solve_wgs[g].size());
-        const size_t had = C->d_bctr.cap;
-        if (int e = C->d_bctr.ensure(groups)) return e;
-        if (C->d_bctr.cap != had) RSC_HIP(hipMemsetAsync(C->d_bctr.p, 0, C->d_bctr.cap * sizeof(unsigned), C->stream));
-        const BetasScratch bs{C->d_berr.p, C->d_bpose.p, C->d_bctr.p, (size_t)total};
+        const BetasScratch bs{C->d_berr.p, C->d_bpose.p, (size_t)total};
         const char* base = C->d_desc.p;
         const DevPnP* dprobs = reinterpret_cast<const DevPnP*>(base + o_probs);
         const LaunchProb* dlps = reinterpret_cast<const LaunchProb*>(base + o_lps);
@@ -618,7 +693,7 @@ struct HipPnPBackend : PnPBackend {
             RSC_HIP(launch_pnp_solve_split(4 + g, (int)quad_wgs[g].size(),
                                           reinterpret_cast<const int2*>(tab + C->pnp_tab_quad[g]), (int)solve_wgs[g].size(),
                                           reinterpret_cast<const int2*>(tab + C->pnp_tab_solve[g]), dprobs, dlps,
-                                          C->d_table.p, C->d_stage.p, C->d_poses.p, C->d_samples.p, bs, C->stream,
+                                          C->d_table.p, C->d_stage.p, C->d_samples.p, bs, C->stream,
                                           eb, C->timing ? C->ev[7 + 2 * g] : nullptr,
                                           (int)quad_wgs[g].size() <= C->eig_rows_max_wgs, C->eig_split,
                                           C->h_flag + kFaultWord, hb));
@@ -626,7 +701,7 @@ struct HipPnPBackend : PnPBackend {
         }
         timing_begin(C, 1);
         RSC_HIP(launch_pnp_scan(ppt, (int)scan_wgs.size(), dprobs, dlps, reinterpret_cast<const int4*>(tab + C->pnp_tab_scan),
-                                C->d_poses.p, cnt_dst, cnt_dev, C->d_masks.p, mw, C->h_qual.p, C->stream));
+                                bs, C->d_poses.p, cnt_dst, cnt_dev, C->d_masks.p, mw, C->h_qual.p, C->stream));
         timing_begin(C, 2);
         if (fused) {
             timing_begin(C, 3);

@@ -118,14 +118,12 @@ constexpr int kEigHyps = RSC_EIG_HYPS;  // hypotheses per 64-lane eigen-stage wo
 // Per-hypothesis stage record between the two kernels: eigenvectors [12][4], alphas [NS][4], cws [4][3].
 constexpr int kStageDoubles = 48 + 24 + 12;
 // Two-kernel hypothesis solve: eigenvectors (lane groups), then the three beta approximations
-// (one wave each) + selection.
-// Hand-off buffers of pnp_betas_kernel: per record and approximation the error (`err[3][hcap]`)
-// and the float pose (`pose[3][12][hcap]`); one counter per 64-hypothesis group, zero between
-// launches (the kernel resets what it uses).
+// (one wave each); the scan selects among them.
+// Results of pnp_betas_kernel, read by pnp_scan_kernel: per approximation and record the error
+// (`err[3][hcap]`) and the float pose (`pose[3][hcap][12]`, a record's 12 floats contiguous).
 struct BetasScratch {
     double* err;
     float* pose;
-    unsigned* ctr;
     size_t hcap;
 };
 // Hypotheses per betas wave: 64.  Smaller waves for small (latency-bound) rounds, and eigen-stage
@@ -141,7 +139,7 @@ constexpr int kBetasHyps = RSC_BETAS_HYPS;
 constexpr int kEigRowsDefaultWgs = 64;
 hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, const int2* wgtB,
                                   const DevPnP* probs, const LaunchProb* lps, const uint32_t* T, double* stage,
-                                  float* poses, int32_t* samples, const BetasScratch& bs, hipStream_t st,
+                                  int32_t* samples, const BetasScratch& bs, hipStream_t st,
                                   hipEvent_t eig_begin = nullptr, hipEvent_t eig_end = nullptr, bool eig_rows = false,
                                   bool eig_split = false, unsigned* fault = nullptr, int betas_hb = kBetasHyps);
 // betas_hb: hypotheses per betas wave (<= kBetasHyps; the wg_table's groups step by it).
@@ -150,9 +148,14 @@ hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, 
 // counts: where the host reads them (pinned memory or HBM); counts_dev (nullable): an HBM copy for
 // pnp_select_refine_kernel; qual[lp] (pinned, zeroed by the host) is set to 1 when a hypothesis of
 // launch problem lp reaches its min_inliers.
+// bs: the betas stage's results; the scan keeps each hypothesis' approximation with the smallest error
+// (a scan workgroup's chunk holds at most 64 hypotheses) and writes its pose to poses[record].
 hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const int4* wgt,
-                           const float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks, int mask_words,
-                           int32_t* qual, hipStream_t st);
+                           const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks,
+                           int mask_words, int32_t* qual, hipStream_t st);
+// Workgroups of pnp_scan_kernel<ppt> one CU holds at once (the runtime's occupancy query for the
+// instantiated kernel: registers and LDS as built).
+hipError_t pnp_scan_occupancy(int ppt, int* wgs_per_cu);
 // fault: the context's fault word (the Refine's split-form eigen hand-off, RSC_REFINE_SPLIT)
 hipError_t launch_pnp_select_refine(int nsel, const DevPnP* probs, const RefineSel* sels, const int32_t* counts,
                                     uint64_t* masks, int mask_words, const float* poses, RefineSelOut* out,

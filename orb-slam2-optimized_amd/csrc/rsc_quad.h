@@ -1052,20 +1052,19 @@ RSC_HD void betas_block(int b, int ngroups, int& g, int& apx) {
 // Kernel 2 (product form): ONE wave per (64 hypotheses, beta approximation), so config 2's 960
 // waves sit one per SIMD instead of 320 three-wave workgroups doubling up on 64 of the 256 CUs.
 // Wave apx runs compute_L_6x10 + find_betas_approx_{apx+1} + gauss_newton + compute_R_and_t
-// (PnPsolver.cpp:383-408) and leaves (error, float pose) in `berr` / `bpose`; the group's last wave
-// to finish (agent-scope counter) keeps the smallest error in the reference's order (:393-414) and
-// writes the pose.  Hand-off: producer stores -> vmcnt(0) -> agent release -> vmcnt(0) -> relaxed
-// agent add; the last adder: agent acquire -> vmcnt(0) -> loads (MI355X_MICROARCH.md, inter-
-// workgroup visibility).  It resets the counter, so every launch starts from zero.
+// (PnPsolver.cpp:383-408) and leaves (error, float pose) in `berr[apx][record]` /
+// `bpose[apx][record][12]`.  The scan behind it in the stream keeps the smallest error in the
+// reference's order (:393-414, pnp_scan_kernel): the kernel boundary is the hand-off, so the waves
+// of a group neither count arrivals nor wait for each other.
 // hb: hypotheses per wave (64 for large rounds; fewer for small ones, so a wave carries the union
 // of fewer data-dependent chains): lanes >= hb mirror lane % hb (same control flow, no writes).
 template <int NS>
 __device__ __forceinline__ void pnp_betas_wave_body(const DevPnP* __restrict__ probs, const LaunchProb* __restrict__ lps,
                                                     const int2* __restrict__ wg_table, int ngroups, int hb,
                                                     const double* __restrict__ stage,
-                                                    const int32_t* __restrict__ samples, float* __restrict__ poses,
+                                                    const int32_t* __restrict__ samples,
                                                     double* __restrict__ berr, float* __restrict__ bpose,
-                                                    unsigned* __restrict__ bctr, size_t hcap, double* smem) {
+                                                    size_t hcap, double* smem) {
     const int lane = threadIdx.x;
     int g, apx;
     betas_block(blockIdx.x, ngroups, g, apx);
@@ -1127,35 +1126,13 @@ __device__ __forceinline__ void pnp_betas_wave_body(const DevPnP* __restrict__ p
     RSC_UNROLL for (int r = 0; r < 3; ++r) pz[9 + r] = (float)t[r];
     if (active) {
         berr[apx * hcap + rec] = err;
-        RSC_UNROLL for (int k = 0; k < 12; ++k) bpose[(apx * 12 + k) * hcap + rec] = pz[k];
+        float4* o = reinterpret_cast<float4*>(bpose + (apx * hcap + rec) * 12);  // 48 B records, 16-B aligned
+        RSC_UNROLL for (int k = 0; k < 3; ++k) o[k] = make_float4(pz[4 * k], pz[4 * k + 1], pz[4 * k + 2], pz[4 * k + 3]);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned prev = 0;
-    if (lane == 0) prev = __hip_atomic_fetch_add(bctr + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    prev = __builtin_amdgcn_readlane(prev, 0);
     RSC_SOLVE_STAMP(1, 6);
 #if RSC_SOLVE_STAMPS
     if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096) g_solve_stamps[1][blockIdx.x][7] = (uint64_t)apx | ((uint64_t)g << 8);
 #endif
-    if (prev != 2) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_store(bctr + g, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!active) return;
-    double e[3];
-    RSC_UNROLL for (int a = 0; a < 3; ++a) e[a] = (a == apx) ? err : berr[a * hcap + rec];
-    int best = 0;
-    double be = e[0];
-    if (e[1] < be) { be = e[1]; best = 1; }
-    if (e[2] < be) { be = e[2]; best = 2; }
-    float* o = poses + rec * 12;
-    if (best == apx) {
-        RSC_UNROLL for (int k = 0; k < 12; ++k) o[k] = pz[k];
-    } else {
-        RSC_UNROLL for (int k = 0; k < 12; ++k) o[k] = bpose[(best * 12 + k) * hcap + rec];
-    }
 }
 
 }  // namespace rsc
