@@ -10,7 +10,8 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fa
 HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
-     facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test
+     facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
+     facade_lastproj_test
 
 $(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
@@ -48,6 +49,10 @@ $(LIBDIR)/localproj.o: $(CSRC)/localproj.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/lastproj.o: $(CSRC)/lastproj.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/kfdb.o: $(CSRC)/kfdb.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -60,7 +65,7 @@ $(LIBDIR)/rsc_api.o: $(CSRC)/rsc_api.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/lastproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 # TEST-ONLY variant: the split eigen stage's hand-off waits give up after one poll, so the fault path
@@ -69,7 +74,7 @@ $(LIBDIR)/kernels_spin1.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DRSC_SPLIT_SPIN_LIMIT=1 -c $< -o $@
 
-$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/lastproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 facade_test: $(LIBDIR)/facade_test
@@ -91,6 +96,11 @@ facade_localproj_test: $(LIBDIR)/facade_localproj_test
 
 $(LIBDIR)/facade_localproj_test: tests/cpp/facade_localproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
 	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_localproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+
+facade_lastproj_test: $(LIBDIR)/facade_lastproj_test
+
+$(LIBDIR)/facade_lastproj_test: tests/cpp/facade_lastproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
+	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_lastproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
 
 facade_voc_test: $(LIBDIR)/facade_voc_test
 
@@ -129,9 +139,12 @@ bowvoc_emu:
 localproj_emu:
 	$(MAKE) -s -C tests/localproj_emu
 
+lastproj_emu:
+	$(MAKE) -s -C tests/lastproj_emu
+
 clean:
 	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
-	       tests/localproj_emu/build
+	       tests/localproj_emu/build tests/lastproj_emu/build
 
-.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu facade_localproj_test facade_test facade_proj_test facade_loopproj_test \
+.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu facade_localproj_test facade_lastproj_test facade_test facade_proj_test facade_loopproj_test \
         facade_voc_test chase_mirror_test clean

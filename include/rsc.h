@@ -750,6 +750,83 @@ int rsc_search_by_projection_points_many(rsc_context* ctx, rsc_frameview* const*
                                          const rsc_track_record* const* track, int32_t* nmatches,
                                          int32_t* n_to_match, int32_t* rounds);
 
+/* ---- Tracking::TrackWithMotionModel: the last-frame matcher and its driver ---------------------------
+ * ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th)
+ * (src/ORBmatcher.cpp:1173-1315) over a resident current Frame (rsc_frameview with rsc_frameview_set_stereo)
+ * and the last Frame's slots (rsc_lastframe).  Every LastFrame slot with a MapPoint that is not an outlier
+ * projects its MapPoint with CurrentFrame.mTcw and takes, among the current features inside th *
+ * scale[LastFrame octave] of the projection (strictly), at the levels of the call's mode, that pass the
+ * stereo gate and hold no MapPoint with observations, the first one of the smallest descriptor distance, if
+ * that is <= TH_HIGH = 100.  The mode is one per call (:1186-1194): 1 forward (tlc.z > mb, octaves >= o), 2
+ * backward (-tlc.z > mb, octaves [0, o]), 0 otherwise (octaves [o-1, o+1]).  A slot whose MapPoint has no
+ * observations takes a feature and blocks nobody: a later slot may take it again, and both count.  The
+ * rotation histogram holds one entry per claim and the removal runs per entry (:1301-1311), so a feature is
+ * left nullptr when ANY of its claimers fell into a removed bin, and the return value is (claims) - (claims in
+ * removed bins).  The reference's sequential order is reproduced exactly.  Precondition: no eligible point
+ * projects to a NaN pixel (camera z == 0 with x == 0 or y == 0, or a non-finite position; undefined in the
+ * reference); such a point is skipped. */
+typedef struct {
+    int32_t n;                 /* LastFrame.N, at most 8192 */
+    const int32_t* octave;     /* [n] mvKeys[i].octave */
+    const float* angle;        /* [n] mvKeysUn[i].angle */
+    const uint8_t* mp_state;   /* [n] 0 = mvpMapPoints[i] is NULL, 1 = set, 2 = set and mvbOutlier[i] */
+    const float* mp_pos;       /* [n][3] GetWorldPos() (read where mp_state != 0) */
+    const uint8_t* mp_desc;    /* [n][32] MapPoint::GetDescriptor(), not the Frame's descriptor row */
+    const uint8_t* mp_has_obs; /* [n] Observations() > 0 */
+} rsc_last_frame_slots;
+
+typedef struct rsc_lastframe rsc_lastframe;
+
+/* Uploads the last Frame as it stands after Tracking::UpdateLastFrame() (src/Tracking.cpp:648-712, which
+ * stays with the caller), once per frame.  n > 8192 is RSC_ERR_ARG. */
+int rsc_lastframe_create(rsc_context* ctx, const rsc_last_frame_slots* slots, rsc_lastframe** out);
+void rsc_lastframe_destroy(rsc_lastframe* view);
+
+/* ORBmatcher.cpp:1173-1315 for c < count in one launch (one workgroup per problem).  Tcw_cur / Tcw_last
+ * [count][16]: CurrentFrame.mTcw / LastFrame.mTcw, row-major; mb[count]: CurrentFrame.mb.  frame_occ[c][f] as
+ * in rsc_search_local_points_many (0, 1 or 2); frame_occ or frame_occ[c] NULL = every slot NULL on entry.
+ * out[c][f] (frames[c] n entries): >= 0 the LastFrame slot whose MapPoint the call leaves in
+ * CurrentFrame.mvpMapPoints[f]; -1 the slot is left as on entry; -2 the rotation check set it to nullptr.
+ * nmatches[c] = the return value; mode[c] (may be NULL) = 0 window, 1 forward, 2 backward; rounds (may be
+ * NULL): fixed-point rounds run (diagnostic, 1 without an eligible slot).  RSC_ERR_ARG, before any launch:
+ * more than 8192 features or slots; a Frame view without rsc_frameview_set_stereo; an octave outside
+ * [0, n_levels) on a slot that has a MapPoint; a non-finite th, or |th| * scale[n_levels-1] * max(grid_w_inv,
+ * grid_h_inv) >= 2^30 (GetFeaturesInArea converts the cell coordinate to int, Frame.cpp:399-411).  count == 0
+ * and a LastFrame without eligible slots are RSC_OK.  With timing enabled, rsc_context_last_kernel_timing
+ * gives [0] the setup kernel, [1] the rounds kernel, [2] both (ms). */
+int rsc_search_by_projection_last_many(rsc_context* ctx, rsc_frameview* const* frames, rsc_lastframe* const* lasts,
+                                       int count, const float* Tcw_cur, const float* Tcw_last, const float* mb,
+                                       const uint8_t* const* frame_occ, float th, int check_orientation,
+                                       int32_t* const* out, int32_t* nmatches, int32_t* mode, int32_t* rounds);
+
+typedef struct {
+    int32_t ok;                 /* the return value of TrackWithMotionModel */
+    int32_t searches;           /* 1 or 2 */
+    int32_t nmatches_search[2]; /* the matcher's return value at th and at 2 * th (-1: did not run) */
+    int32_t mode;               /* as rsc_search_by_projection_last_many */
+    int32_t nmatches;           /* after the outlier discard (Tracking.cpp:761) */
+    int32_t nmatches_map;       /* nmatchesMap (:763-764) */
+    int32_t vo;                 /* mbVO = nmatchesMap < 10, set with only_tracking (:770); else 0 */
+    int32_t n_good;             /* PoseOptimization's return value (0 when it did not run) */
+    float Tcw[16];              /* mCurrentFrame.mTcw afterwards (Tcw_cur when PoseOptimization did not run) */
+} rsc_track_motion_result;
+
+/* Tracking::TrackWithMotionModel (src/Tracking.cpp:724-774) for `count` frames: one search launch at th from
+ * an empty mvpMapPoints (:724-732), one at 2 * th, again from empty, over the frames with nmatches < 20
+ * (:735-739), one rsc_pose_optimization_many launch over the frames that reached 20 (:745), and the discard
+ * loop (:749-766) on the host.  Tcw_cur = mVelocity * mLastFrame.mTcw as the caller computed it (:722).  th =
+ * 15 or 7 (:728-731); only_tracking[count] = mbOnlyTracking of each frame's Tracking object.  A frame that
+ * stays below 20 has ok = 0 and its second search's matches in out[c], as the reference leaves them
+ * (slots the rotation check nulled read -1).  out[c][f]: the LastFrame slot in
+ * mvpMapPoints[f] after the discard, else -1; discarded[c][f]: the LastFrame slot whose MapPoint was removed
+ * as an outlier (the caller sets its mbTrackInView = false and mnLastFrameSeen), else -1.  nmatches starts
+ * from the matcher's return value, double counts included, as in the reference.  Arguments are checked as in
+ * rsc_search_by_projection_last_many, for th and 2 * th. */
+int rsc_track_motion_model_many(rsc_context* ctx, rsc_frameview* const* frames, rsc_lastframe* const* lasts,
+                                int count, const float* Tcw_cur, const float* Tcw_last, const float* mb, float th,
+                                const int32_t* only_tracking, rsc_track_motion_result* result,
+                                int32_t* const* out, int32_t* const* discarded);
+
 /* ---- KeyFrameDatabase: BoW candidate scoring (src/KeyFrameDatabase.cpp) ---------------------- */
 /* A device-resident keyframe database: each KeyFrame is a slot in [0, capacity) holding its
  * BowVector (word ids ascending, TF-IDF values, DBoW2 L1_NORM scoring), its

@@ -36,6 +36,13 @@
 // mTrackProjX, mTrackProjY, mTrackProjXR, mnTrackScaleLevel, mTrackViewCos; the helper writes those back and
 // calls IncreaseVisible().  The points must be distinct and non-null (mvpLocalMapPoints is built through
 // mnTrackReferenceForFrame, Tracking.cpp:1041-1062, which guarantees both).
+//
+// SearchByProjection(CurrentFrame, LastFrame, th) (ORBmatcher.cpp:1173-1315; Tracking.cpp:732,738) and the
+// helper rsc_orb::TrackWithMotionModel (Tracking.cpp:724-774) read of the last Frame N, mvKeys[i].octave,
+// mvKeysUn[i].angle, mvpMapPoints, mvbOutlier and mTcw, per MapPoint GetWorldPos(), GetDescriptor() and
+// Observations(), and of the current Frame additionally mb; the helper also needs mnId, mvbOutlier, mTcw(r, c)
+// and SetPose as rsc_orb::PoseOptimization does, and writes mbTrackInView / mnLastFrameSeen on the MapPoints it
+// discards as outliers.
 #pragma once
 #include <algorithm>
 #include <memory>
@@ -246,6 +253,62 @@ FrameViewUpload upload_frameview(const FrameT& F) {
     u.n = n;
     check(rsc_frameview_create(thread_context(), &f, &u.h), "rsc_frameview_create");
     return u;
+}
+
+// The last Frame's slots as SearchByProjection(CurrentFrame, LastFrame, th) reads them (rsc_lastframe_create).
+struct LastFrameUpload {
+    rsc_lastframe* h = nullptr;
+    int n = 0;
+    LastFrameUpload() = default;
+    LastFrameUpload(const LastFrameUpload&) = delete;
+    LastFrameUpload& operator=(const LastFrameUpload&) = delete;
+    LastFrameUpload(LastFrameUpload&& o) noexcept : h(o.h), n(o.n) { o.h = nullptr; }
+    ~LastFrameUpload() { rsc_lastframe_destroy(h); }
+};
+
+template <class FrameT>
+LastFrameUpload upload_lastframe(const FrameT& L) {
+    const size_t n = (size_t)L.N;
+    std::vector<int32_t> oct(n, 0);
+    std::vector<float> ang(n, 0.f), pos(3 * n, 0.f);
+    std::vector<uint8_t> state(n, 0), desc(32 * n, 0), has_obs(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        oct[i] = L.mvKeys[i].octave;   // ORBmatcher.cpp:1223 reads mvKeys,
+        ang[i] = L.mvKeysUn[i].angle;  // :1278 mvKeysUn
+        if (i >= L.mvpMapPoints.size() || !L.mvpMapPoints[i]) continue;  // :1200
+        auto& mp = *L.mvpMapPoints[i];
+        state[i] = i < L.mvbOutlier.size() && L.mvbOutlier[i] ? 2 : 1;  // :1202
+        const auto X = mp.GetWorldPos();
+        for (int c = 0; c < 3; ++c) pos[3 * i + c] = X(c);
+        const auto d = mp.GetDescriptor();
+        const uint8_t* dr = d.template ptr<uint8_t>(0);
+        std::copy(dr, dr + 32, desc.begin() + 32 * i);
+        has_obs[i] = mp.Observations() > 0 ? 1 : 0;
+    }
+    rsc_last_frame_slots s;
+    s.n = (int32_t)n;
+    s.octave = oct.data();
+    s.angle = ang.data();
+    s.mp_state = state.data();
+    s.mp_pos = pos.data();
+    s.mp_desc = desc.data();
+    s.mp_has_obs = has_obs.data();
+    LastFrameUpload u;
+    u.n = (int)n;
+    check(rsc_lastframe_create(thread_context(), &s, &u.h), "rsc_lastframe_create");
+    return u;
+}
+
+template <class IsoT>
+void iso_to_array16(const IsoT& S, float* T) {
+    const auto R = S.rotation();
+    const auto t = S.translation();
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) T[4 * r + k] = R(r, k);
+        T[4 * r + 3] = t(r);
+    }
+    T[12] = T[13] = T[14] = 0.f;
+    T[15] = 1.f;
 }
 
 }  // namespace detail
@@ -704,6 +767,41 @@ public:
         return local_points(F, vpMapPoints, th, mfNNratio, false, 0.f, nullptr);
     }
 
+    // SearchByProjection(CurrentFrame, LastFrame, th) (ORBmatcher.cpp:1173-1315; Tracking.cpp:732,738): every
+    // LastFrame slot with a MapPoint that is not an outlier is matched around its projection with
+    // CurrentFrame.mTcw, at the levels of the call's mode (forward / backward / neither, from the two poses and
+    // CurrentFrame.mb).  Writes CurrentFrame.mvpMapPoints, the nullptr of the rotation check included, and
+    // returns the count (claims minus claims in removed rotation bins, as the reference counts).
+    template <class FrameT>
+    int SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th) {
+        detail::FrameViewUpload fv = detail::upload_frameview(CurrentFrame);
+        check(rsc_frameview_set_stereo(fv.h, CurrentFrame.mvuRight.data(), CurrentFrame.mbf),
+              "rsc_frameview_set_stereo");
+        detail::LastFrameUpload lv = detail::upload_lastframe(LastFrame);
+        const size_t nf = (size_t)fv.n;
+        std::vector<uint8_t> occ(nf > 0 ? nf : 1, 0);
+        for (size_t f = 0; f < nf && f < CurrentFrame.mvpMapPoints.size(); ++f)  // :1248-1250
+            if (CurrentFrame.mvpMapPoints[f]) occ[f] = CurrentFrame.mvpMapPoints[f]->Observations() > 0 ? 2 : 1;
+        std::vector<int32_t> out(nf > 0 ? nf : 1, -1);
+        float Tc[16], Tl[16];
+        iso_to_array(CurrentFrame.mTcw, Tc);
+        iso_to_array(LastFrame.mTcw, Tl);
+        const float mb = CurrentFrame.mb;
+        rsc_frameview* hf = fv.h;
+        rsc_lastframe* hl = lv.h;
+        const uint8_t* pocc = occ.data();
+        int32_t* pout = out.data();
+        int32_t nm = 0;
+        check(rsc_search_by_projection_last_many(thread_context(), &hf, &hl, 1, Tc, Tl, &mb, &pocc, th,
+                                                 mbCheckOrientation ? 1 : 0, &pout, &nm, nullptr, nullptr),
+              "SearchByProjection(CurrentFrame, LastFrame)");
+        for (size_t f = 0; f < nf && f < CurrentFrame.mvpMapPoints.size(); ++f) {
+            if (out[f] >= 0) CurrentFrame.mvpMapPoints[f] = LastFrame.mvpMapPoints[out[f]];  // :1273
+            else if (out[f] == -2) CurrentFrame.mvpMapPoints[f] = nullptr;                   // :1307
+        }
+        return nm;
+    }
+
     // Tracking::SearchLocalPoints from :1003 on (Tracking.cpp:1003-1028) in one device call: isInFrustum(pMP,
     // 0.5) over the points with mnLastFrameSeen != F.mnId that are not bad, the track members and
     // IncreaseVisible() on the MapPoints as the reference leaves them, then the matcher when nToMatch > 0.
@@ -796,14 +894,7 @@ private:
 
     template <class IsoT>
     static void iso_to_array(const IsoT& S, float* T) {
-        const auto R = S.rotation();
-        const auto t = S.translation();
-        for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k) T[4 * r + k] = R(r, k);
-            T[4 * r + 3] = t(r);
-        }
-        T[12] = T[13] = T[14] = 0.f;
-        T[15] = 1.f;
+        detail::iso_to_array16(S, T);
     }
 
     float mfNNratio;
@@ -816,6 +907,58 @@ template <class FrameT, class MPPtr>
 int SearchLocalPoints(FrameT& F, const std::vector<MPPtr>& vpLocalMapPoints, float th, float nnratio = 0.8f,
                       int* nToMatch = nullptr) {
     return ORBmatcher::SearchLocalPoints(F, vpLocalMapPoints, th, nnratio, nToMatch);
+}
+
+// Tracking::TrackWithMotionModel from :724 to its return value (Tracking.cpp:724-774) in one device call:
+// mvpMapPoints cleared, SearchByProjection(CurrentFrame, LastFrame, th) with ORBmatcher(0.9, true), the retry at
+// 2 * th when fewer than 20 matched, Optimizer::PoseOptimization, and the discard loop.  The caller has run
+// UpdateLastFrame() (:720) and CurrentFrame.SetPose(mVelocity * LastFrame.mTcw) (:722).  Writes
+// CurrentFrame.mvpMapPoints, mvbOutlier and the pose (SetPose), and mbTrackInView = false / mnLastFrameSeen =
+// CurrentFrame.mnId on the MapPoints discarded as outliers.  bVO receives mbVO when bOnlyTracking is set and the
+// optimisation ran (:770); returns the function's value.  FrameT additionally needs mb, mnId, mvbOutlier,
+// mTcw(r, c) and SetPose as rsc_orb::PoseOptimization does.
+template <class FrameT>
+bool TrackWithMotionModel(FrameT& CurrentFrame, const FrameT& LastFrame, int th, bool bOnlyTracking,
+                          bool* bVO = nullptr, rsc_track_motion_result* record = nullptr) {
+    detail::FrameViewUpload fv = detail::upload_frameview(CurrentFrame);
+    check(rsc_frameview_set_stereo(fv.h, CurrentFrame.mvuRight.data(), CurrentFrame.mbf), "rsc_frameview_set_stereo");
+    detail::LastFrameUpload lv = detail::upload_lastframe(LastFrame);
+    const size_t nf = (size_t)fv.n;
+    std::vector<int32_t> out(nf > 0 ? nf : 1, -1), disc(nf > 0 ? nf : 1, -1);
+    float Tc[16], Tl[16];
+    detail::iso_to_array16(CurrentFrame.mTcw, Tc);
+    detail::iso_to_array16(LastFrame.mTcw, Tl);
+    const float mb = CurrentFrame.mb;
+    const int32_t only = bOnlyTracking ? 1 : 0;
+    rsc_frameview* hf = fv.h;
+    rsc_lastframe* hl = lv.h;
+    int32_t* pout = out.data();
+    int32_t* pdisc = disc.data();
+    rsc_track_motion_result r;
+    check(rsc_track_motion_model_many(thread_context(), &hf, &hl, 1, Tc, Tl, &mb, (float)th, &only, &r, &pout, &pdisc),
+          "TrackWithMotionModel");
+    CurrentFrame.mvpMapPoints.assign(CurrentFrame.mvpMapPoints.size(), nullptr);  // :724
+    if (CurrentFrame.mvbOutlier.size() < nf) CurrentFrame.mvbOutlier.resize(nf, false);
+    for (size_t f = 0; f < nf && f < CurrentFrame.mvpMapPoints.size(); ++f) {
+        if (out[f] >= 0) {
+            CurrentFrame.mvpMapPoints[f] = LastFrame.mvpMapPoints[out[f]];
+            if (r.nmatches_search[r.searches - 1] >= 20) CurrentFrame.mvbOutlier[f] = false;  // Optimizer.cpp:255
+        } else if (disc[f] >= 0) {  // :753-761
+            auto& mp = *LastFrame.mvpMapPoints[disc[f]];
+            CurrentFrame.mvbOutlier[f] = false;
+            mp.mbTrackInView = false;
+            mp.mnLastFrameSeen = CurrentFrame.mnId;
+        }
+    }
+    if (r.nmatches_search[r.searches - 1] >= 20) {  // PoseOptimization ran: pFrame->SetPose (Optimizer.cpp:420-421)
+        auto T = CurrentFrame.mTcw;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) T(a, b) = r.Tcw[4 * a + b];
+        CurrentFrame.SetPose(T);
+        if (bOnlyTracking && bVO) *bVO = r.vo != 0;  // :770
+    }
+    if (record) *record = r;
+    return r.ok != 0;
 }
 
 }  // namespace rsc_orb

@@ -27,6 +27,7 @@
 #include "rsc_frameproj.h"
 #include "rsc_kfproj.h"
 #include "rsc_localproj.h"
+#include "rsc_lastproj.h"
 #include "rsc_sim3compose.h"
 #include "rsc_kfdb.h"
 #include "rsc_bowvoc.h"
@@ -2819,8 +2820,10 @@ struct rsc_frameview {
     std::vector<int32_t> octave;
     float K[4];
     DevBuf<float> d_uright;  // mvuRight (rsc_frameview_set_stereo)
+    std::vector<float> h_uright;  // its host copy (the motion-model driver's PoseOptimization problems)
     float mbf = 0.0f;
     bool has_stereo = false;
+    float top_scale = 1.0f, gw_inv = 0.0f, gh_inv = 0.0f;  // the radius guard of the last-frame matcher
 };
 
 int rsc_frameview_create(rsc_context* C, const rsc_frame_features* f, rsc_frameview** out) {
@@ -2882,6 +2885,9 @@ int rsc_frameview_create(rsc_context* C, const rsc_frame_features* f, rsc_framev
         v->inv_level_sigma2[l] = 1.0f / s2;
     }
     v->K[0] = f->fx; v->K[1] = f->fy; v->K[2] = f->cx; v->K[3] = f->cy;
+    v->top_scale = f->scale_factors[f->n_levels - 1];
+    v->gw_inv = f->grid_w_inv;
+    v->gh_inv = f->grid_h_inv;
     *out = v.release();
     return RSC_OK;
 }
@@ -2908,6 +2914,7 @@ int rsc_frameview_set_stereo(rsc_frameview* v, const float* u_right, float mbf) 
     if (int e = v->d_uright.ensure((size_t)std::max(v->n, 1))) return e;
     RSC_HIP(hipStreamSynchronize(v->ctx->stream));
     if (v->n) RSC_HIP(hipMemcpy(v->d_uright.p, u_right, 4 * (size_t)v->n, hipMemcpyHostToDevice));
+    v->h_uright.assign(u_right, u_right + (v->n > 0 ? v->n : 0));
     v->mbf = mbf;
     v->has_stereo = true;
     return RSC_OK;
@@ -4800,5 +4807,313 @@ int rsc_search_by_projection_points_many(rsc_context* C, rsc_frameview* const* f
                                          int32_t* nmatches, int32_t* n_to_match, int32_t* rounds) {
     return local_points_impl(C, frames, points, count, nullptr, skip, has_obs, frame_occ, 0.0f, th, nn_ratio, out,
                              const_cast<rsc_track_record* const*>(track), nmatches, n_to_match, rounds, false);
+}
+
+// ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th) (ORBmatcher.cpp:1173-1315, rsc_lastproj.h) ----
+struct rsc_lastframe {
+    rsc_context* ctx = nullptr;
+    int n = 0;
+    DevBuf<char> mem;  // octave | angle | mp_state | mp_pos | mp_desc | mp_has_obs
+    DevLastFrame dev;  // device pointers
+    // host copies: the argument check and the motion-model driver read them
+    std::vector<int32_t> octave;
+    std::vector<uint8_t> mp_state, mp_has_obs;
+    std::vector<float> mp_pos;
+};
+
+int rsc_lastframe_create(rsc_context* C, const rsc_last_frame_slots* s, rsc_lastframe** out) {
+    if (!C || !s || !out) return RSC_ERR_ARG;
+    *out = nullptr;
+    if (s->n < 0) return RSC_ERR_ARG;
+    if (s->n > kLastMaxSlots) {
+        g_last_error = "LastFrame with more than 8192 slots";
+        return RSC_ERR_ARG;
+    }
+    if (s->n > 0 && (!s->octave || !s->angle || !s->mp_state || !s->mp_pos || !s->mp_desc || !s->mp_has_obs))
+        return RSC_ERR_ARG;
+    const size_t n = (size_t)s->n;
+    S3Blob b;
+    const size_t o_oct = b.add(s->octave, 4 * n), o_ang = b.add(s->angle, 4 * n), o_st = b.add(s->mp_state, n);
+    const size_t o_pos = b.add(s->mp_pos, 12 * n), o_d = b.add(s->mp_desc, 32 * n), o_ho = b.add(s->mp_has_obs, n);
+    b.reserve(256);  // n == 0: a non-empty allocation
+    std::unique_ptr<rsc_lastframe> v(new rsc_lastframe);
+    v->ctx = C;
+    v->n = s->n;
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = v->mem.ensure(b.h.size())) return e;
+    char* d = v->mem.p;
+    v->dev.octave = reinterpret_cast<const int32_t*>(d + o_oct);
+    v->dev.angle = reinterpret_cast<const float*>(d + o_ang);
+    v->dev.mp_state = reinterpret_cast<const uint8_t*>(d + o_st);
+    v->dev.mp_pos = reinterpret_cast<const float*>(d + o_pos);
+    v->dev.mp_desc = reinterpret_cast<const ProjDesc*>(d + o_d);
+    v->dev.mp_has_obs = reinterpret_cast<const uint8_t*>(d + o_ho);
+    v->dev.n = s->n;
+    RSC_HIP(hipMemcpy(d, b.h.data(), b.h.size(), hipMemcpyHostToDevice));
+    if (n) {
+        v->octave.assign(s->octave, s->octave + n);
+        v->mp_state.assign(s->mp_state, s->mp_state + n);
+        v->mp_has_obs.assign(s->mp_has_obs, s->mp_has_obs + n);
+        v->mp_pos.assign(s->mp_pos, s->mp_pos + 3 * n);
+    }
+    *out = v.release();
+    return RSC_OK;
+}
+
+void rsc_lastframe_destroy(rsc_lastframe* v) {
+    if (!v) return;
+    (void)hipStreamSynchronize(v->ctx->stream);
+    delete v;
+}
+
+namespace {
+// what rsc_search_by_projection_last_many refuses before any launch
+int last_check_args(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts, int count, float th) {
+    // GetFeaturesInArea converts (u - mnMinX + r) * mfGridElementWidthInv to int, undefined out of int's
+    // range: the u term is below 64 cells, so the radius term is kept below 2^30 cells
+    if (!std::isfinite(th)) {
+        g_last_error = "th is not finite";
+        return RSC_ERR_ARG;
+    }
+    for (int c = 0; c < count; ++c) {
+        if (!frames[c] || !lasts[c] || frames[c]->ctx != C || lasts[c]->ctx != C) return RSC_ERR_ARG;
+        const rsc_frameview& f = *frames[c];
+        const rsc_lastframe& l = *lasts[c];
+        if (f.n > kLastMaxFeatures || l.n > kLastMaxSlots) {
+            g_last_error = "more than 8192 features or LastFrame slots";
+            return RSC_ERR_ARG;
+        }
+        if (!f.has_stereo) {
+            g_last_error = "Frame view without mvuRight / mbf (rsc_frameview_set_stereo)";
+            return RSC_ERR_ARG;
+        }
+        if (!(std::fabs(th) * f.top_scale * std::max(f.gw_inv, f.gh_inv) < 1073741824.0f)) {
+            g_last_error = "last-frame SearchByProjection radius out of the grid arithmetic's range";
+            return RSC_ERR_ARG;
+        }
+        const int n_levels = (int)f.inv_level_sigma2.size();
+        for (int i = 0; i < l.n; ++i)
+            if (l.mp_state[i] != 0 && (l.octave[i] < 0 || l.octave[i] >= n_levels)) {
+                g_last_error = "LastFrame keypoint octave out of range on a slot with a MapPoint";
+                return RSC_ERR_ARG;
+            }
+    }
+    return 0;
+}
+}  // namespace
+
+int rsc_search_by_projection_last_many(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts,
+                                       int count, const float* Tcw_cur, const float* Tcw_last, const float* mb,
+                                       const uint8_t* const* frame_occ, float th, int check_orientation,
+                                       int32_t* const* out, int32_t* nmatches, int32_t* mode, int32_t* rounds) {
+    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!frames || !lasts || !Tcw_cur || !Tcw_last || !mb || !out) return RSC_ERR_ARG;
+    if (int e = last_check_args(C, frames, lasts, count, th)) return e;
+    for (int c = 0; c < count; ++c)
+        if (frames[c]->n && !out[c]) return RSC_ERR_ARG;
+    // layout: problem table | frame_occ  (uploaded)  | windows | candidates | claims  (scratch)  |
+    // out | nmatches, mode, rounds, claims  (what comes back)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    std::vector<size_t> o_oc(count), o_rec(count), o_cd(count), o_cl(count), o_out(count), o_cnt(count);
+    int max_slots = 0;
+    size_t off = al(sizeof(LastProjProblem) * count);
+    for (int c = 0; c < count; ++c) {
+        o_oc[c] = off; off = al(off + (size_t)std::max(frames[c]->n, 1));
+    }
+    const size_t up = off;
+    for (int c = 0; c < count; ++c) {
+        const size_t nl = (size_t)std::max(lasts[c]->n, 1);
+        o_rec[c] = off; off = al(off + sizeof(LpRec) * nl);
+        o_cd[c] = off; off = al(off + sizeof(ProjCand) * nl);
+        o_cl[c] = off; off = al(off + 4 * nl);
+        max_slots = std::max(max_slots, lasts[c]->n);
+    }
+    const size_t back = off;
+    for (int c = 0; c < count; ++c) {
+        o_out[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
+        o_cnt[c] = off; off += 16;
+    }
+    const size_t bytes = al(off);
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = C->d_fp.ensure(bytes)) return e;
+    if (int e = C->h_fp.ensure(bytes)) return e;
+    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
+    char* h = C->h_fp.p;
+    char* d = C->d_fp.p;
+    for (int c = 0; c < count; ++c) {
+        const rsc_frameview& f = *frames[c];
+        const rsc_lastframe& l = *lasts[c];
+        if (frame_occ && frame_occ[c]) {
+            if (f.n) std::memcpy(h + o_oc[c], frame_occ[c], (size_t)f.n);
+        } else {
+            std::memset(h + o_oc[c], 0, (size_t)std::max(f.n, 1));
+        }
+        LastProjProblem p;
+        p.F = f.hdr;
+        p.u_right = f.d_uright.p;
+        p.mbf = f.mbf;
+        p.mode = last_mode(Tcw_cur + 16 * (size_t)c, Tcw_last + 16 * (size_t)c, mb[c]);
+        p.L = l.dev;
+        std::memcpy(p.Tcw, Tcw_cur + 16 * (size_t)c, sizeof(p.Tcw));
+        p.frame_occ = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
+        p.rec = reinterpret_cast<LpRec*>(d + o_rec[c]);
+        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+        p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+        std::memcpy(h + sizeof(LastProjProblem) * c, &p, sizeof(p));
+    }
+    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
+    timing_begin(C, 3);
+    RSC_HIP(launch_search_by_projection_last(count, max_slots, reinterpret_cast<const LastProjProblem*>(d), th,
+                                             check_orientation ? 1 : 0, C->timing ? C->ev[5] : nullptr, C->stream));
+    timing_begin(C, 4);
+    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    if (C->timing) {  // rsc_context_last_kernel_timing: [0] setup kernel, [1] rounds kernel, [2] both
+        float ms = 0, a = 0, b = 0;
+        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
+        (void)hipEventElapsedTime(&a, C->ev[3], C->ev[5]);
+        (void)hipEventElapsedTime(&b, C->ev[5], C->ev[4]);
+        C->last_ms[0] = a;
+        C->last_ms[1] = b;
+        C->last_ms[2] = ms;
+    }
+    for (int c = 0; c < count; ++c) {
+        if (frames[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)frames[c]->n);
+        if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
+        if (mode) std::memcpy(&mode[c], h + o_cnt[c] + 4, 4);
+        if (rounds) std::memcpy(&rounds[c], h + o_cnt[c] + 8, 4);
+    }
+    return RSC_OK;
+}
+
+// Tracking::TrackWithMotionModel (Tracking.cpp:724-774); each stage one launch over the frames still in it.
+int rsc_track_motion_model_many(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts, int count,
+                                const float* Tcw_cur, const float* Tcw_last, const float* mb, float th,
+                                const int32_t* only_tracking, rsc_track_motion_result* result, int32_t* const* out,
+                                int32_t* const* discarded) {
+    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!frames || !lasts || !Tcw_cur || !Tcw_last || !mb || !only_tracking || !result || !out || !discarded)
+        return RSC_ERR_ARG;
+    if (int e = last_check_args(C, frames, lasts, count, th)) return e;
+    if (int e = last_check_args(C, frames, lasts, count, 2.0f * th)) return e;
+    for (int c = 0; c < count; ++c)
+        if (frames[c]->n && (!out[c] || !discarded[c])) return RSC_ERR_ARG;
+    std::vector<int32_t> nm(count), md(count);
+    // :724-732: from an empty mvpMapPoints (frame_occ NULL)
+    if (int st = rsc_search_by_projection_last_many(C, frames, lasts, count, Tcw_cur, Tcw_last, mb, nullptr, th, 1,
+                                                    out, nm.data(), md.data(), nullptr))
+        return st;
+    std::vector<int> again, opt;
+    for (int c = 0; c < count; ++c) {
+        rsc_track_motion_result& r = result[c];
+        std::memset(&r, 0, sizeof(r));
+        r.searches = 1;
+        r.nmatches_search[0] = nm[c];
+        r.nmatches_search[1] = -1;
+        r.mode = md[c];
+        r.nmatches = nm[c];
+        std::memcpy(r.Tcw, Tcw_cur + 16 * (size_t)c, sizeof(r.Tcw));
+        for (int f = 0; f < frames[c]->n; ++f) discarded[c][f] = -1;
+        if (nm[c] < 20) again.push_back(c);  // :735
+    }
+    if (!again.empty()) {  // :737-738: again from empty, at 2 * th
+        const int m = (int)again.size();
+        std::vector<rsc_frameview*> F(m);
+        std::vector<rsc_lastframe*> L(m);
+        std::vector<float> Tc(16 * (size_t)m), Tl(16 * (size_t)m), b(m);
+        std::vector<int32_t*> op(m);
+        std::vector<int32_t> nm2(m);
+        for (int q = 0; q < m; ++q) {
+            const int c = again[q];
+            F[q] = frames[c];
+            L[q] = lasts[c];
+            std::memcpy(&Tc[16 * (size_t)q], Tcw_cur + 16 * (size_t)c, 16 * sizeof(float));
+            std::memcpy(&Tl[16 * (size_t)q], Tcw_last + 16 * (size_t)c, 16 * sizeof(float));
+            b[q] = mb[c];
+            op[q] = out[c];
+        }
+        if (int st = rsc_search_by_projection_last_many(C, F.data(), L.data(), m, Tc.data(), Tl.data(), b.data(),
+                                                        nullptr, 2.0f * th, 1, op.data(), nm2.data(), nullptr, nullptr))
+            return st;
+        for (int q = 0; q < m; ++q) {
+            rsc_track_motion_result& r = result[again[q]];
+            r.searches = 2;
+            r.nmatches_search[1] = nm2[q];
+            r.nmatches = nm2[q];
+        }
+    }
+    for (int c = 0; c < count; ++c) {
+        for (int f = 0; f < frames[c]->n; ++f)
+            if (out[c][f] < 0) out[c][f] = -1;  // a slot the rotation check nulled is empty
+        if (result[c].nmatches >= 20) opt.push_back(c);  // :741
+    }
+    if (opt.empty()) return RSC_OK;
+    // :745 Optimizer::PoseOptimization(&mCurrentFrame) on every occupied slot
+    const int m = (int)opt.size();
+    std::vector<std::vector<uint8_t>> has(m), outl(m);
+    std::vector<std::vector<float>> Xw(m), inv(m);
+    std::vector<rsc_poseopt_problem> pr(m);
+    std::vector<rsc_poseopt_result> res(m);
+    std::vector<uint8_t*> olp(m);
+    for (int q = 0; q < m; ++q) {
+        const int c = opt[q];
+        const rsc_frameview& F = *frames[c];
+        const rsc_lastframe& L = *lasts[c];
+        const size_t n = (size_t)F.n;
+        has[q].assign(std::max(n, (size_t)1), 0);
+        outl[q].assign(std::max(n, (size_t)1), 0);
+        Xw[q].assign(3 * std::max(n, (size_t)1), 0.f);
+        inv[q].assign(std::max(n, (size_t)1), 0.f);
+        for (size_t f = 0; f < n; ++f) {
+            const int32_t s = out[c][f];
+            if (s < 0) continue;
+            has[q][f] = 1;
+            for (int k = 0; k < 3; ++k) Xw[q][3 * f + k] = L.mp_pos[3 * (size_t)s + k];
+            inv[q][f] = F.inv_level_sigma2[F.octave[f]];
+        }
+        rsc_poseopt_problem& P = pr[q];
+        P.n = F.n;
+        P.has_mp = has[q].data();
+        P.uv = F.kp.data();
+        P.Xw = Xw[q].data();
+        P.inv_sigma2 = inv[q].data();
+        P.u_right = F.h_uright.data();
+        P.fx = F.K[0]; P.fy = F.K[1]; P.cx = F.K[2]; P.cy = F.K[3];
+        std::memcpy(P.Tcw, result[c].Tcw, sizeof(P.Tcw));
+        P.bf = F.mbf;
+        olp[q] = outl[q].data();
+    }
+    if (int st = rsc_pose_optimization_many(C, pr.data(), m, res.data(), olp.data())) return st;
+    for (int q = 0; q < m; ++q) {
+        const int c = opt[q];
+        const rsc_lastframe& L = *lasts[c];
+        rsc_track_motion_result& r = result[c];
+        r.n_good = res[q].n_good;
+        std::memcpy(r.Tcw, res[q].Tcw, sizeof(r.Tcw));
+        int map = 0;
+        for (int f = 0; f < frames[c]->n; ++f) {  // :749-766
+            const int32_t s = out[c][f];
+            if (s < 0) continue;
+            if (outl[q][f]) {
+                discarded[c][f] = s;
+                out[c][f] = -1;
+                r.nmatches--;
+            } else if (L.mp_has_obs[s]) {
+                ++map;
+            }
+        }
+        r.nmatches_map = map;
+        if (only_tracking[c]) {  // :768-772
+            r.vo = map < 10;
+            r.ok = r.nmatches > 20;
+        } else {
+            r.ok = map >= 10;  // :774
+        }
+    }
+    return RSC_OK;
 }
 }  // extern "C"

@@ -60,6 +60,8 @@ EXPORTED = [
     "rsc_voc_create", "rsc_voc_destroy", "rsc_voc_size", "rsc_voc_info", "rsc_voc_transform_many",
     "rsc_voc_last_kernel_timing", "rsc_bow_create_transformed",
     "rsc_frameview_set_stereo", "rsc_search_local_points_many", "rsc_search_by_projection_points_many",
+    "rsc_lastframe_create", "rsc_lastframe_destroy", "rsc_search_by_projection_last_many",
+    "rsc_track_motion_model_many",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -417,6 +419,93 @@ def search_by_projection_points_many(ctx: Context, frames, points, track, skip, 
     """The bare ORBmatcher::SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cpp:16-100) on the host's track
     members (TRACK_RECORD [points n] per problem, not modified); otherwise as search_local_points_many."""
     return _local_points(ctx, frames, points, None, skip, has_obs, frame_occ, 0.0, th, nn_ratio, track)
+
+
+class LastFrameSlots(C.Structure):
+    """rsc_last_frame_slots (include/rsc.h)."""
+    _fields_ = [("n", C.c_int32), ("octave", C.c_void_p), ("angle", C.c_void_p), ("mp_state", C.c_void_p),
+                ("mp_pos", C.c_void_p), ("mp_desc", C.c_void_p), ("mp_has_obs", C.c_void_p)]
+
+
+class TrackMotionResult(C.Structure):
+    """rsc_track_motion_result (include/rsc.h)."""
+    _fields_ = [("ok", C.c_int32), ("searches", C.c_int32), ("nmatches_search", C.c_int32 * 2), ("mode", C.c_int32),
+                ("nmatches", C.c_int32), ("nmatches_map", C.c_int32), ("vo", C.c_int32), ("n_good", C.c_int32),
+                ("Tcw", C.c_float * 16)]
+
+
+class LastFrameView:
+    """The last Frame as the motion-model matcher reads it, resident in HBM (rsc_lastframe_create): an object
+    with n, octave int32 [n] (mvKeys), angle float32 [n] (mvKeysUn), mp_state uint8 [n] (0 NULL, 1 set, 2 set
+    and mvbOutlier), mp_pos float32 [n,3], mp_desc uint8 [n,32] (MapPoint::GetDescriptor), mp_has_obs uint8 [n]."""
+
+    def __init__(self, ctx: Context, last):
+        self.ctx, self.n = ctx, int(last.n)
+        pad = lambda a, dt, k: (np.ascontiguousarray(a, dt).reshape(-1) if self.n else np.zeros(k, dt))
+        keep = [pad(last.octave, np.int32, 1), pad(last.angle, np.float32, 1), pad(last.mp_state, np.uint8, 1),
+                pad(last.mp_pos, np.float32, 3), pad(last.mp_desc, np.uint8, 32), pad(last.mp_has_obs, np.uint8, 1)]
+        m = LastFrameSlots()
+        m.n = self.n
+        m.octave, m.angle, m.mp_state, m.mp_pos, m.mp_desc, m.mp_has_obs = (a.ctypes.data for a in keep)
+        h = C.c_void_p()
+        _check(load_library().rsc_lastframe_create(ctx.h, C.byref(m), C.byref(h)), "rsc_lastframe_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().rsc_lastframe_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def _poses(T, c):
+    return np.ascontiguousarray(np.asarray(T, np.float32).reshape(c, 16)) if c else np.zeros((1, 16), np.float32)
+
+
+def search_by_projection_last_many(ctx: Context, frames, lasts, Tcw_cur, Tcw_last, mb, frame_occ=None,
+                                   th: float = 7.0, check_orientation: bool = True):
+    """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th) (ORBmatcher.cpp:1173-1315) for each (FrameView
+    with set_stereo, LastFrameView, Tcw_cur [4,4], Tcw_last [4,4], mb, frame_occ uint8 [frame n] or None = all
+    NULL) in one launch.  Returns a dict of per-problem lists / arrays: out (int32 [frame n]: >= 0 the LastFrame
+    slot left in mvpMapPoints[f], -1 untouched, -2 set to nullptr by the rotation check), nmatches, mode (0
+    window, 1 forward, 2 backward), rounds."""
+    c = len(frames)
+    if frame_occ is None:
+        frame_occ = [None] * c
+    oc = [np.zeros(max(f.n, 1), np.uint8) if a is None or not f.n else np.ascontiguousarray(a, np.uint8)
+          for a, f in zip(frame_occ, frames)]
+    out = [np.full(max(f.n, 1), -7, np.int32) for f in frames]
+    nm, mode, rounds = (np.zeros(max(c, 1), np.int32) for _ in range(3))
+    b = np.ascontiguousarray(mb, np.float32).reshape(-1) if c else np.zeros(1, np.float32)
+    assert b.size == max(c, 1)
+    _check(load_library().rsc_search_by_projection_last_many(
+        ctx.h, _handles(frames), _handles(lasts), c, _poses(Tcw_cur, c), _poses(Tcw_last, c), b, _ptrs(oc),
+        float(th), int(check_orientation), _ptrs(out), nm, mode, rounds), "rsc_search_by_projection_last_many")
+    return dict(out=[o[:f.n] for o, f in zip(out, frames)], nmatches=nm[:c], mode=mode[:c], rounds=rounds[:c])
+
+
+def track_motion_model_many(ctx: Context, frames, lasts, Tcw_cur, Tcw_last, mb, th: float = 7.0,
+                            only_tracking=None):
+    """Tracking::TrackWithMotionModel (Tracking.cpp:724-774, rsc_track_motion_model_many) for each (FrameView
+    with set_stereo, LastFrameView after UpdateLastFrame, Tcw_cur = mVelocity * mLastFrame.mTcw, Tcw_last, mb,
+    only_tracking = mbOnlyTracking per frame, default all false).  Returns (TrackMotionResult records, list of out
+    int32 [frame n] after the discard, list of discarded int32 [frame n])."""
+    c = len(frames)
+    out = [np.full(max(f.n, 1), -7, np.int32) for f in frames]
+    disc = [np.full(max(f.n, 1), -7, np.int32) for f in frames]
+    b = np.ascontiguousarray(mb, np.float32).reshape(-1) if c else np.zeros(1, np.float32)
+    assert b.size == max(c, 1)
+    res = (TrackMotionResult * max(c, 1))()
+    ot = np.zeros(max(c, 1), np.int32)
+    if only_tracking is not None and c:
+        ot[:] = np.asarray(only_tracking, np.int32).reshape(c)
+    _check(load_library().rsc_track_motion_model_many(
+        ctx.h, _handles(frames), _handles(lasts), c, _poses(Tcw_cur, c), _poses(Tcw_last, c), b, float(th),
+        ot, res, _ptrs(out), _ptrs(disc)), "rsc_track_motion_model_many")
+    return (np.ctypeslib.as_array(res).copy()[:c], [o[:f.n] for o, f in zip(out, frames)],
+            [d[:f.n] for d, f in zip(disc, frames)])
 
 
 def fuse_sim3_many(ctx: Context, kfs, points, Scw, in_kf, th: float):
@@ -792,6 +881,15 @@ def load_library(path: str = LIB_PATH):
         [C.POINTER(C.c_void_p)] * 3 + [C.c_float] * 3 + [C.POINTER(C.c_void_p)] * 2 + [i32p] * 3
     L.rsc_search_by_projection_points_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int] + \
         [C.POINTER(C.c_void_p)] * 3 + [C.c_float] * 2 + [C.POINTER(C.c_void_p)] * 2 + [i32p] * 3
+    L.rsc_lastframe_create.argtypes = [vp, C.POINTER(LastFrameSlots), C.POINTER(vp)]
+    L.rsc_lastframe_destroy.argtypes = [vp]
+    L.rsc_lastframe_destroy.restype = None
+    L.rsc_search_by_projection_last_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_, f32p_, f32p_,
+                                                     C.POINTER(C.c_void_p), C.c_float, C.c_int,
+                                                     C.POINTER(C.c_void_p), i32p, i32p, i32p]
+    L.rsc_track_motion_model_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_, f32p_, f32p_,
+                                              C.c_float, i32p, C.POINTER(TrackMotionResult),
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.rsc_voc_create.argtypes = [vp, C.POINTER(VocabularyNodes), C.POINTER(vp)]
     L.rsc_voc_destroy.argtypes = [vp]
     L.rsc_voc_destroy.restype = None
