@@ -13,51 +13,10 @@ all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu 
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
      facade_lastproj_test
 
-$(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+OBJS = $(addprefix $(LIBDIR)/,kernels.o mlpnp.o poseopt.o sim3opt.o orbmatch.o sim3match.o frameproj.o kfproj.o \
+         localproj.o lastproj.o kfdb.o bowvoc.o rsc_api.o)
 
-$(LIBDIR)/mlpnp.o: $(CSRC)/mlpnp.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/poseopt.o: $(CSRC)/poseopt.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/orbmatch.o: $(CSRC)/orbmatch.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/sim3match.o: $(CSRC)/sim3match.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/frameproj.o: $(CSRC)/frameproj.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/kfproj.o: $(CSRC)/kfproj.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/localproj.o: $(CSRC)/localproj.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/lastproj.o: $(CSRC)/lastproj.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/kfdb.o: $(CSRC)/kfdb.hip $(HDRS)
-	mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/bowvoc.o: $(CSRC)/bowvoc.hip $(HDRS)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -65,7 +24,7 @@ $(LIBDIR)/rsc_api.o: $(CSRC)/rsc_api.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIBDIR)/librsc.so: $(LIBDIR)/kernels.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/lastproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 # TEST-ONLY variant: the split eigen stage's hand-off waits give up after one poll, so the fault path
@@ -74,38 +33,16 @@ $(LIBDIR)/kernels_spin1.o: $(CSRC)/kernels.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DRSC_SPLIT_SPIN_LIMIT=1 -c $< -o $@
 
-$(LIBDIR)/librsc_spin1.so: $(LIBDIR)/kernels_spin1.o $(LIBDIR)/mlpnp.o $(LIBDIR)/poseopt.o $(LIBDIR)/sim3opt.o $(LIBDIR)/orbmatch.o $(LIBDIR)/sim3match.o $(LIBDIR)/frameproj.o $(LIBDIR)/kfproj.o $(LIBDIR)/localproj.o $(LIBDIR)/lastproj.o $(LIBDIR)/kfdb.o $(LIBDIR)/bowvoc.o $(LIBDIR)/rsc_api.o
+$(LIBDIR)/librsc_spin1.so: $(OBJS:%/kernels.o=%/kernels_spin1.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
-facade_test: $(LIBDIR)/facade_test
+FACADE_TESTS = facade_test facade_proj_test facade_loopproj_test facade_localproj_test facade_lastproj_test \
+               facade_voc_test
 
-$(LIBDIR)/facade_test: tests/cpp/facade_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
-	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+$(FACADE_TESTS): %: $(LIBDIR)/%
 
-facade_proj_test: $(LIBDIR)/facade_proj_test
-
-$(LIBDIR)/facade_proj_test: tests/cpp/facade_proj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
-	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_proj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
-
-facade_loopproj_test: $(LIBDIR)/facade_loopproj_test
-
-$(LIBDIR)/facade_loopproj_test: tests/cpp/facade_loopproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
-	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_loopproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
-
-facade_localproj_test: $(LIBDIR)/facade_localproj_test
-
-$(LIBDIR)/facade_localproj_test: tests/cpp/facade_localproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
-	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_localproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
-
-facade_lastproj_test: $(LIBDIR)/facade_lastproj_test
-
-$(LIBDIR)/facade_lastproj_test: tests/cpp/facade_lastproj_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
-	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_lastproj_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
-
-facade_voc_test: $(LIBDIR)/facade_voc_test
-
-$(LIBDIR)/facade_voc_test: tests/cpp/facade_voc_test.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
-	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ tests/cpp/facade_voc_test.cpp -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+$(FACADE_TESTS:%=$(LIBDIR)/%): $(LIBDIR)/%: tests/cpp/%.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
+	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ $< -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
 
 # TEST-ONLY host programs: tridiag_qr with and without the mirror() / any_lane() hooks of its
 # rotation sink (tests/test_cpu_chase_mirror.py); the second build runs under the host sanitizers

@@ -1,7 +1,9 @@
 // frameproj.hip — ORBmatcher::SearchByProjection(Frame&, KeyFrame, sAlreadyFound, th, ORBdist) kernel
-// (src/ORBmatcher.cpp:1317-1444); see rsc_frameproj.h for the mapping and the fixed-point argument.
+// (src/ORBmatcher.cpp:1317-1444); see rsc_frameproj.h for what this matcher sets and rsc_projcore.h for the
+// mapping and the fixed-point argument.
 #include <hip/hip_runtime.h>
 #include "rsc_frameproj.h"
+#include "rsc_projrounds.h"
 
 namespace rsc {
 
@@ -11,24 +13,15 @@ namespace {
 __global__ __launch_bounds__(256) void frameproj_setup_kernel(const FrameProjProblem* __restrict__ problems, float th,
                                                               int orb_dist) {
     const FrameProjProblem& P = problems[blockIdx.y];
-    const DevProjFrame& F = *P.F;
-    const DevProjKF& K = P.K;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= K.n) return;
-    ProjRec q = proj_no_window();
-    ProjCand cd;
-    cd.c[0] = cd.c[1] = cd.c[2] = cd.c[3] = -1;
-    if (proj_eligible(K, P.already, i)) {
-        q = proj_setup(F, K, P.Tcw, i, th);
-        if (q.cells >= 0) {
-            const ProjDesc d = K.mp_desc[i];
-            if (proj_candidates(F, q, d, P.frame_mp, orb_dist, cd)) q.cells |= kProjMore;
-        }
-    }
-    P.rec[i] = q;
-    P.cand[i] = cd;
-    P.claim[i] = -1;
+    if (i < P.K.n) proj_setup_point(P, i, th, orb_dist);
 }
+
+// the pre-occupied bits in LDS
+struct ProjOccBits {
+    const uint32_t* w;
+    RSCM_HD bool operator()(int f) const { return (w[f >> 5] >> (f & 31)) & 1u; }
+};
 
 // One workgroup per (Frame, KeyFrame) problem.  LDS: the owner table over the Frame's features (32 KB),
 // the pre-occupied bits (1 KB) and the rotation histogram; the MapPoints' cached windows, candidates and
@@ -39,7 +32,7 @@ __global__ __launch_bounds__(kProjThreads) void frameproj_kernel(const FrameProj
     __shared__ uint32_t occ[kProjMaxFeatures / 32];
     __shared__ int hist[kProjHistoLength];
     __shared__ int keep[3];
-    __shared__ int n_eligible, changed, total;
+    __shared__ int n_eligible, total;
 
     const FrameProjProblem& P = problems[blockIdx.x];
     const DevProjFrame& F = *P.F;
@@ -58,46 +51,11 @@ __global__ __launch_bounds__(kProjThreads) void frameproj_kernel(const FrameProj
         if (P.frame_mp[f] >= 0) atomicOr(&occ[f >> 5], 1u << (f & 31));
         P.out[f] = -1;
     }
-    // the MapPoints with a window: only they can claim (the bound of the loop below)
-    int mine = 0;
-    for (int i = tid; i < nK; i += kProjThreads) mine += P.rec[i].cells >= 0;
-    if (mine) atomicAdd(&n_eligible, mine);
+    proj_count_eligible<kProjThreads>(P.rec, nK, &n_eligible);
     __syncthreads();
 
-    const int max_rounds = n_eligible + 1;
-    int rounds = 0;
-    for (int r = 0; r < max_rounds; ++r) {
-        for (int f = tid; f < nF; f += kProjThreads)
-            owner[f] = (occ[f >> 5] >> (f & 31)) & 1u ? kProjOccupied : kProjFree;
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        for (int i = tid; i < nK; i += kProjThreads) {
-            const int a = P.claim[i];
-            if (a >= 0) atomicMin(&owner[a], i);
-        }
-        __syncthreads();
-        int any = 0;
-        for (int i = tid; i < nK; i += kProjThreads) {
-            const int cells = P.rec[i].cells;
-            if (cells < 0) continue;
-            const ProjCand cd = P.cand[i];
-            int b = proj_pick(cd, (cells & kProjMore) != 0, i, owner);
-            if (b == -2) {  // the cached four are taken and there were more: walk the window
-                const ProjDesc d = K.mp_desc[i];
-                b = proj_best(F, P.rec[i], d, i, owner, orb_dist);
-            }
-            if (b != P.claim[i]) {
-                P.claim[i] = b;
-                any = 1;
-            }
-        }
-        if (any) changed = 1;
-        ++rounds;
-        __syncthreads();
-        const int go = changed;
-        __syncthreads();
-        if (!go) break;
-    }
+    const int rounds = proj_rounds<kProjThreads>(FrameRounds<ProjOccBits>{P, orb_dist, ProjOccBits{occ}}, owner, nF,
+                                                 P.claim, n_eligible, nullptr);
     // `owner` is the table of the final claims (the last round changed none): owner[A[i]] == i
 
     // rotation histogram (:1405-1415), ComputeThreeMaxima (:1428), removal (:1430-1440)
@@ -110,13 +68,13 @@ __global__ __launch_bounds__(kProjThreads) void frameproj_kernel(const FrameProj
         }
         __syncthreads();
         if (tid == 0) {
-            int hs[kProjHistoLength];
+            int hs[kProjHistoLength], k3[3];
 #pragma unroll
             for (int b = 0; b < kProjHistoLength; ++b) hs[b] = hist[b];
-            const int m = proj_three_maxima(hs, kProjHistoLength);
-            keep[0] = (m & 255) - 1;
-            keep[1] = ((m >> 8) & 255) - 1;
-            keep[2] = ((m >> 16) & 255) - 1;
+            proj_keep_bins(hs, k3);
+            keep[0] = k3[0];
+            keep[1] = k3[1];
+            keep[2] = k3[2];
         }
         __syncthreads();
     }

@@ -4458,6 +4458,7 @@ DevKfpKF kfp_kf_of(const rsc_kfview& k) {
     DevKfpKF K;
     K.kp = reinterpret_cast<const ProjPt*>(k.dev.kp);
     K.octave = k.dev.octave;
+    K.angle = nullptr;  // no rotation check in the loop-closing matchers
     K.desc = reinterpret_cast<const ProjDesc*>(k.dev.desc);
     K.cell_begin = k.dev.cell_begin;
     K.cell_feat = k.dev.cell_feat;

@@ -5,16 +5,13 @@
 // arithmetic, shared by kfproj.hip and the host emulation (tests/kfproj_emu).
 //
 // SearchByProjection is sequentially greedy: point i skips the keypoints that earlier points of the call
-// wrote to vpMatched (:324).  The mapping and the fixed-point argument are those at the head of
-// rsc_frameproj.h with the points in the MapPoint role and the KeyFrame's keypoints in the feature role:
-// one workgroup per (KeyFrame, point set) problem iterates
-//     A[i] = first minimum descriptor distance over the candidates f of point i with
-//            owner[f] = min{ j : A[j] == f } >= i      (kept if <= TH_LOW)
-// where a keypoint with vpMatched[f] != NULL on entry carries kProjOccupied.  Point 0 is final after round
-// 1, points 0..i after round i + 1, so the fixed point is the sequential result and is reached in at most
-// n_eligible + 1 rounds.  Keeping only candidates with distance <= TH_LOW is sound: a point takes its
-// minimum over the free keypoints first and applies the cutoff afterwards, so a candidate above the
-// cutoff can only ever produce "no match", which is what an exhausted list produces too.
+// wrote to vpMatched (:324).  Mapping, visiting order, candidate cache and the fixed-point argument:
+// rsc_projcore.h, with the points in the point role and the KeyFrame's keypoints in the feature role.  What
+// this matcher sets: every claimer blocks; a keypoint with vpMatched[f] != NULL on entry is occupied; levels
+// [L-1, L]; the decision is "first free minimum, kept if <= TH_LOW"; the finish keeps owner[A[i]] == i.
+// Keeping only candidates with distance <= TH_LOW in the cache is sound: a point takes its minimum over the
+// free keypoints first and applies the cutoff afterwards, so a candidate above the cutoff can only ever produce
+// "no match", which is what an exhausted list produces too.
 // Fuse has no such coupling (it never skips a keypoint): one lane per (point, KeyFrame) pair.
 //
 // What differs from the Frame matcher (rsc_frameproj.h), line by line below: z < 0 is rejected; invz is a
@@ -41,16 +38,16 @@ constexpr int kKfpThLow = 50;          // ORBmatcher::TH_LOW (ORBmatcher.cpp:7)
 constexpr int kKfpMaxKeypoints = kProjMaxFeatures;  // KeyFrame::N bound (the LDS owner table)
 constexpr int kKfpThreads = 512;
 
-// the KeyFrame as the two matchers read it (the keypoint side of rsc_kfview)
-struct DevKfpKF {
-    const ProjPt* kp;           // [n] mvKeysUn[i].pt
-    const int32_t* octave;      // [n]
-    const ProjDesc* desc;       // [n] mDescriptors rows
-    const int32_t* cell_begin;  // [64*48 + 1] mGrid as CSR, cell = ix * 48 + iy
-    const int32_t* cell_feat;
-    const float* scale;         // [n_levels] mvScaleFactors
-    float min_x, max_x, min_y, max_y, gw_inv, gh_inv, fx, fy, cx, cy, log_sf;
-    int n, n_levels;
+// The KeyFrame as the two matchers read it (the keypoint side of rsc_kfview): the Frame view with angle == NULL
+// (no rotation check).  A type of its own only for the constructor, which takes the fields without the angle.
+struct DevKfpKF : DevProjFrame {
+    DevKfpKF() = default;
+    RSCM_HD DevKfpKF(const ProjPt* kp, const int32_t* octave, const ProjDesc* desc, const int32_t* cell_begin,
+                     const int32_t* cell_feat, const float* scale, float min_x, float max_x, float min_y, float max_y,
+                     float gw_inv, float gh_inv, float fx, float fy, float cx, float cy, float log_sf, int n,
+                     int n_levels)
+        : DevProjFrame{kp, octave, nullptr, desc, cell_begin, cell_feat, scale, min_x, max_x, min_y, max_y,
+                       gw_inv, gh_inv, fx, fy, cx, cy, log_sf, n, n_levels} {}
 };
 
 // vpPoints (rsc_mpview)
@@ -127,24 +124,12 @@ RSCM_HD ProjRec kfp_setup(const DevKfpKF& K, const DevKfpPoints& P, const float*
     if (level < 0) level = 0;
     else if (level >= K.n_levels) level = K.n_levels - 1;
     const float r = th * K.scale[level];
-    int x0 = (int)floorf((u - K.min_x - r) * K.gw_inv);
-    if (x0 < 0) x0 = 0;
-    if (x0 >= kProjGridCols) return q;
-    int x1 = (int)ceilf((u - K.min_x + r) * K.gw_inv);
-    if (x1 > kProjGridCols - 1) x1 = kProjGridCols - 1;
-    if (x1 < 0) return q;
-    int y0 = (int)floorf((v - K.min_y - r) * K.gh_inv);
-    if (y0 < 0) y0 = 0;
-    if (y0 >= kProjGridRows) return q;
-    int y1 = (int)ceilf((v - K.min_y + r) * K.gh_inv);
-    if (y1 > kProjGridRows - 1) y1 = kProjGridRows - 1;
-    if (y1 < 0) return q;
     ProjRec w;
     w.u = u;
     w.v = v;
     w.r = r;
-    w.cells = x0 | x1 << 6 | y0 << 12 | y1 << 18 | level << 24;
-    return w;
+    w.cells = proj_cells(K, u, v, r, level);
+    return w.cells < 0 ? q : w;
 }
 
 // SearchByProjection uses Scw as toIso left it (:250-251); Fuse divides by the scale (:832-835).
@@ -159,71 +144,57 @@ RSCM_HD void kfp_decompose(const float* S, bool fuse, float* R, float* t) {
     }
 }
 
-// :319-343 / :906-928 over the window of `q`: the keypoint point i takes when the keypoints with
-// owner[f] < i are not available, or -1.  bestDist starts at 256 (:319) or INT_MAX (:906); with the
-// cutoff at TH_LOW the two give the same answer.
-template <class OwnerPtr>
-RSCM_HD int kfp_best(const DevKfpKF& K, const ProjRec& q, const ProjDesc& dMP, int i, OwnerPtr owner) {
-    if (q.cells < 0) return -1;
-    const int x0 = q.cells & 63, x1 = (q.cells >> 6) & 63, y0 = (q.cells >> 12) & 63, y1 = (q.cells >> 18) & 63;
-    const int level = (q.cells >> 24) & 63;
-    int bestDist = 256, bestIdx = -1;
-    for (int ix = x0; ix <= x1; ++ix)
-        for (int iy = y0; iy <= y1; ++iy) {
-            const int c = ix * kProjGridRows + iy;
-            const int e1 = K.cell_begin[c + 1];
-            for (int e = K.cell_begin[c]; e < e1; ++e) {
-                const int f = K.cell_feat[e];
-                const ProjPt kp = K.kp[f];
-                if (!(fabsf(kp.x - q.u) < q.r && fabsf(kp.y - q.v) < q.r)) continue;  // KeyFrame.cpp:589-593
-                if (owner[f] < i) continue;                                            // :324
-                const int oct = K.octave[f];
-                if (oct < level - 1 || oct > level) continue;                          // :329 / :913, [L-1, L]
-                const int dist = proj_desc_dist(dMP, K.desc[f]);
-                if (dist < bestDist) {
-                    bestDist = dist;
-                    bestIdx = f;
-                }
-            }
-        }
-    return bestDist <= kKfpThLow ? bestIdx : -1;
+// the static gates of point q: the window (KeyFrame.cpp:589-593) and levels [L-1, L] (:329 / :913)
+RSCM_HD ProjGate kfp_gate(const DevKfpKF& K, const ProjRec& q) {
+    const int level = ProjCells(q.cells).level;
+    return ProjGate(K, q.u, q.v, q.r, level - 1, level);
 }
 
-// The walk of kfp_best once, for all rounds: the four smallest (distance, visiting order) among the
-// candidates with distance <= TH_LOW on keypoints that are free before the call.  Returns true when more
-// than four qualified.
+// :319-343 / :906-928 over the window of `q`: the keypoint point i takes when the keypoints with owner[f] < i
+// are not available, or -1.  bestDist starts at 256 (:319) or INT_MAX (:906); with the cutoff at TH_LOW the two
+// give the same answer.
+template <class OwnerPtr>
+RSCM_HD int kfp_best(const DevKfpKF& K, const ProjRec& q, const ProjDesc& dMP, int i, OwnerPtr owner) {
+    return proj_first_min(K, q.cells, dMP, i, owner, kfp_gate(K, q), kKfpThLow);
+}
+
+// the cache of point q: distance <= TH_LOW on keypoints free before the call; true when more than four qualified
 RSCM_HD bool kfp_candidates(const DevKfpKF& K, const ProjRec& q, const ProjDesc& dMP, const uint8_t* occupied,
                             ProjCand& out) {
-    const int x0 = q.cells & 63, x1 = (q.cells >> 6) & 63, y0 = (q.cells >> 12) & 63, y1 = (q.cells >> 18) & 63;
-    const int level = (q.cells >> 24) & 63;
-    int k0 = INT_MAX, k1 = INT_MAX, k2 = INT_MAX, k3 = INT_MAX, count = 0;
-    for (int ix = x0; ix <= x1; ++ix)
-        for (int iy = y0; iy <= y1; ++iy) {
-            const int c = ix * kProjGridRows + iy;
-            const int e1 = K.cell_begin[c + 1];
-            for (int e = K.cell_begin[c]; e < e1; ++e) {
-                const int f = K.cell_feat[e];
-                const ProjPt kp = K.kp[f];
-                if (!(fabsf(kp.x - q.u) < q.r && fabsf(kp.y - q.v) < q.r)) continue;
-                if (occupied[f]) continue;
-                const int oct = K.octave[f];
-                if (oct < level - 1 || oct > level) continue;
-                const int dist = proj_desc_dist(dMP, K.desc[f]);
-                if (dist > kKfpThLow) continue;
-                ++count;
-                const int key = dist << 16 | f;  // a strict < keeps equal distances in visiting order
-                if (dist < (k0 >> 16)) { k3 = k2; k2 = k1; k1 = k0; k0 = key; }
-                else if (dist < (k1 >> 16)) { k3 = k2; k2 = k1; k1 = key; }
-                else if (dist < (k2 >> 16)) { k3 = k2; k2 = key; }
-                else if (dist < (k3 >> 16)) { k3 = key; }
-            }
-        }
-    out.c[0] = k0 == INT_MAX ? -1 : k0;
-    out.c[1] = k1 == INT_MAX ? -1 : k1;
-    out.c[2] = k2 == INT_MAX ? -1 : k2;
-    out.c[3] = k3 == INT_MAX ? -1 : k3;
-    return count > 4;
+    return proj_candidates(K, q.cells, dMP, kfp_gate(K, q), [occupied](int f) { return occupied[f] != 0; },
+                           kKfpThLow, out);
 }
+
+// What the rounds share, for point i: the window, the cache and an empty claim
+RSCM_HD void kfp_setup_point(const KfProjProblem& Q, int i, float th) {
+    ProjRec q = proj_no_window();
+    ProjCand cd = proj_no_cand();
+    if (kfp_eligible(Q.P, Q.already, i)) {
+        float R[9], t[3];
+        kfp_decompose(Q.Scw, false, R, t);
+        q = kfp_setup(Q.K, Q.P, R, t, i, th, false);
+        if (q.cells >= 0 && kfp_candidates(Q.K, q, Q.P.desc[i], Q.occupied, cd)) q.cells |= kProjMore;
+    }
+    Q.rec[i] = q;
+    Q.cand[i] = cd;
+    Q.claim[i] = -1;
+}
+
+// the matcher of the rounds (rsc_projrounds.h)
+struct KfpRounds {
+    static constexpr bool kCoopWalk = false;
+    const KfProjProblem& Q;
+    RSCM_HD int n_points() const { return Q.P.n; }
+    RSCM_HD bool entry_occupied(int f) const { return Q.occupied[f] != 0; }
+    RSCM_HD bool blocks(int) const { return true; }  // :324
+    RSCM_HD int pick(int i, const int* owner) const {
+        const int cells = Q.rec[i].cells;
+        return cells < 0 ? kProjSkip : proj_pick(Q.cand[i], (cells & kProjMore) != 0, i, owner);
+    }
+    RSCM_HD int best(int i, const int* owner) const {  // :319-343
+        return kfp_best(Q.K, Q.rec[i], Q.P.desc[i], i, owner);
+    }
+};
 
 // Fuse for one (point, KeyFrame) pair: bestIdx when bestDist <= TH_LOW, else -1 (:846-928)
 RSCM_HD int kfp_fuse_point(const DevKfpKF& K, const DevKfpPoints& P, const float* Scw, const uint8_t* in_kf, int i,
@@ -233,8 +204,7 @@ RSCM_HD int kfp_fuse_point(const DevKfpKF& K, const DevKfpPoints& P, const float
     kfp_decompose(Scw, true, R, t);
     const ProjRec q = kfp_setup(K, P, R, t, i, th, true);
     if (q.cells < 0) return -1;
-    const ProjDesc d = P.desc[i];
-    return kfp_best(K, q, d, i, KfpAllFree());
+    return kfp_best(K, q, P.desc[i], i, KfpAllFree());
 }
 
 #if defined(__HIPCC__)

@@ -15,22 +15,16 @@
 //   acceptance   bestDist <= TH_HIGH (:1271); every accepted claim is one rotHist entry (:1276-1286)
 //
 // Occupancy depends on the occupant as in rsc_localproj.h: a slot whose MapPoint has no observations (the
-// visual-odometry points of UpdateLastFrame) takes a feature and blocks nobody, so
-//     f is skipped by point i  <=>  min{ j : A[j] == f, has_obs[j] } < i
-// with kProjOccupied for an entry occupant with observations.  The decision is "first free minimum, then
-// cutoff" as in rsc_frameproj.h.  Fixed point: one workgroup per problem iterates
-//     A[i] = first free minimum of point i's candidates f with owner[f] >= i   (kept if <= TH_HIGH)
-// Point i reads only the claims of points j < i, so point 0 is final after round 1 and points 0..i after round
-// i + 1: the fixed point is unique, equals the sequential result and is reached in at most n_eligible + 1
-// rounds (the last one only confirms).  A plain bounded loop: no cross-workgroup hand-off, nothing to wait for.
+// visual-odometry points of UpdateLastFrame) takes a feature and blocks nobody.  Mapping, visiting order and
+// the fixed-point argument: rsc_projcore.h, with the owner rule "only claimers with observations block",
+// kProjOccupied for an entry occupant with observations, and the decision "first free minimum, kept if <=
+// TH_HIGH" as in rsc_frameproj.h.
 //
-// Candidate cache: the four smallest (distance, visiting order) candidates with distance <= TH_HIGH on
-// features without an entry occupant that has observations.  TH_HIGH IS a sound filter here, unlike in
-// rsc_localproj.h: the point takes its minimum over the free features first and applies the cutoff
-// afterwards, and there is no runner-up test.  If the free minimum is above TH_HIGH the point claims nothing,
-// and so it does when every free candidate was dropped; if it is <= TH_HIGH it was kept, and every kept
-// candidate sorts before every dropped one.  When all four cached candidates are taken by lower slots and
-// there were more, the window is walked again (last_best; on the device by 16 lanes, last_best_coop).
+// Candidate cache: distance <= TH_HIGH.  TH_HIGH IS a sound filter here, unlike in rsc_localproj.h: the point
+// takes its minimum over the free features first and applies the cutoff afterwards, and there is no runner-up
+// test.  If the free minimum is above TH_HIGH the point claims nothing, and so it does when every free
+// candidate was dropped; if it is <= TH_HIGH it was kept.  When all four cached candidates are taken by lower
+// slots and there were more, the window is walked again (on the device by 16 lanes).
 //
 // Rotation check (:1292-1312).  The histogram holds one entry PER CLAIM, overwritten claims included, and
 // the removal runs per entry: mvpMapPoints[f] ends up nullptr when ANY claimer of f fell into a removed bin,
@@ -109,11 +103,7 @@ RSCM_HD bool last_eligible(const DevLastFrame& L, int i) { return L.mp_state[i] 
 // :1205-1226 and the cell range of GetFeaturesInArea (Frame.cpp:399-413).  The slot's octave must be in
 // [0, F.n_levels).
 RSCM_HD LpRec last_setup(const DevProjFrame& F, float mbf, const DevLastFrame& L, const float* T, int i, float th) {
-    LpRec q;
-    q.u = q.v = q.r = q.xr = 0.0f;
-    q.cells = -1;
-    q.in_view = 0;
-    q.pad[0] = q.pad[1] = 0;
+    LpRec q = lp_no_window();
     const float pw[3] = {L.mp_pos[3 * i], L.mp_pos[3 * i + 1], L.mp_pos[3 * i + 2]};
     float pc[3];
 #pragma unroll
@@ -134,107 +124,67 @@ RSCM_HD LpRec last_setup(const DevProjFrame& F, float mbf, const DevLastFrame& L
     q.v = v;
     q.r = r;
     q.xr = u - mbf * invzc;                            // :1254
-    int x0 = (int)floorf((u - F.min_x - r) * F.gw_inv);
-    if (x0 < 0) x0 = 0;
-    if (x0 >= kProjGridCols) return q;
-    int x1 = (int)ceilf((u - F.min_x + r) * F.gw_inv);
-    if (x1 > kProjGridCols - 1) x1 = kProjGridCols - 1;
-    if (x1 < 0) return q;
-    int y0 = (int)floorf((v - F.min_y - r) * F.gh_inv);
-    if (y0 < 0) y0 = 0;
-    if (y0 >= kProjGridRows) return q;
-    int y1 = (int)ceilf((v - F.min_y + r) * F.gh_inv);
-    if (y1 > kProjGridRows - 1) y1 = kProjGridRows - 1;
-    if (y1 < 0) return q;
-    q.cells = x0 | x1 << 6 | y0 << 12 | y1 << 18 | o << 24;
+    q.cells = proj_cells(F, u, v, r, o);
     return q;
 }
 
-// The gates of one (point, feature) pair that do not depend on the claims: the level bounds and the strict
-// window of GetFeaturesInArea (Frame.cpp:428-441), then the stereo gate (:1252-1258)
-RSCM_HD bool last_static_gate(const DevProjFrame& F, const float* u_right, const LpRec& q, int lo, int hi, int f) {
-    const int oct = F.octave[f];
-    if (oct < lo || oct > hi) return false;
-    const ProjPt kp = F.kp[f];
-    if (!(fabsf(kp.x - q.u) < q.r && fabsf(kp.y - q.v) < q.r)) return false;
-    const float ur = u_right[f];
-    if (ur > 0.0f) {                        // :1252
-        const float er = fabsf(q.xr - ur);  // :1255
-        if (er > q.r) return false;         // :1256, strict
-    }
-    return true;
+// the static gates of slot q: the level bounds of the mode, the window, then the stereo gate (:1252-1258)
+RSCM_HD ProjStereoGate last_gate(const DevProjFrame& F, const float* u_right, const LpRec& q, int mode) {
+    int lo, hi;
+    last_levels(mode, ProjCells(q.cells).level, lo, hi);
+    return ProjStereoGate{ProjGate(F, q.u, q.v, q.r, lo, hi), u_right, q.xr};
 }
 
-// :1242-1271 over the window of `q`: the feature point i takes when the features with owner[f] < i are skipped
-// (an entry occupant with observations carries kProjOccupied), or -1
+// :1242-1271 over the window of `q`: the feature slot i takes when the features with owner[f] < i are skipped, or -1
 template <class OwnerPtr>
 RSCM_HD int last_best(const DevProjFrame& F, const float* u_right, const LpRec& q, const ProjDesc& dMP, int i,
                       OwnerPtr owner, int mode) {
-    if (q.cells < 0) return -1;
-    const int x0 = q.cells & 63, x1 = (q.cells >> 6) & 63, y0 = (q.cells >> 12) & 63, y1 = (q.cells >> 18) & 63;
-    int lo, hi;
-    last_levels(mode, (q.cells >> 24) & 63, lo, hi);
-    int bestDist = 256, bestIdx = -1;
-    for (int ix = x0; ix <= x1; ++ix)
-        for (int iy = y0; iy <= y1; ++iy) {
-            const int c = ix * kProjGridRows + iy;
-            const int e1 = F.cell_begin[c + 1];
-            for (int e = F.cell_begin[c]; e < e1; ++e) {
-                const int f = F.cell_feat[e];
-                if (!last_static_gate(F, u_right, q, lo, hi, f)) continue;
-                if (owner[f] < i) continue;  // :1248-1250
-                const int dist = proj_desc_dist(dMP, F.desc[f]);
-                if (dist < bestDist) {       // :1264
-                    bestDist = dist;
-                    bestIdx = f;
-                }
-            }
-        }
-    return bestDist <= kLpThHigh ? bestIdx : -1;  // :1271
+    return proj_first_min(F, q.cells, dMP, i, owner, last_gate(F, u_right, q, mode), kLpThHigh);
 }
 
-// The walk of last_best once, for all rounds: the four smallest (distance, visiting order) among the
-// candidates with distance <= TH_HIGH on features without an entry occupant that has observations.  Returns
-// true when more than four qualified.  One round's choice from the cache is proj_pick (rsc_frameproj.h).
+// the cache of slot q: distance <= TH_HIGH on features without an entry occupant that has observations; true when
+// more than four qualified
 RSCM_HD bool last_candidates(const DevProjFrame& F, const float* u_right, const LpRec& q, const ProjDesc& dMP,
                              const uint8_t* frame_occ, int mode, ProjCand& out) {
-    const int x0 = q.cells & 63, x1 = (q.cells >> 6) & 63, y0 = (q.cells >> 12) & 63, y1 = (q.cells >> 18) & 63;
-    int lo, hi;
-    last_levels(mode, (q.cells >> 24) & 63, lo, hi);
-    int k0 = INT_MAX, k1 = INT_MAX, k2 = INT_MAX, k3 = INT_MAX, count = 0;
-    for (int ix = x0; ix <= x1; ++ix)
-        for (int iy = y0; iy <= y1; ++iy) {
-            const int c = ix * kProjGridRows + iy;
-            const int e1 = F.cell_begin[c + 1];
-            for (int e = F.cell_begin[c]; e < e1; ++e) {
-                const int f = F.cell_feat[e];
-                if (!last_static_gate(F, u_right, q, lo, hi, f)) continue;
-                if (frame_occ[f] == 2) continue;
-                const int dist = proj_desc_dist(dMP, F.desc[f]);
-                if (dist > kLpThHigh) continue;
-                ++count;
-                const int key = dist << 16 | f;  // a strict < keeps equal distances in visiting order
-                if (dist < (k0 >> 16)) { k3 = k2; k2 = k1; k1 = k0; k0 = key; }
-                else if (dist < (k1 >> 16)) { k3 = k2; k2 = k1; k1 = key; }
-                else if (dist < (k2 >> 16)) { k3 = k2; k2 = key; }
-                else if (dist < (k3 >> 16)) { k3 = key; }
-            }
-        }
-    out.c[0] = k0 == INT_MAX ? -1 : k0;
-    out.c[1] = k1 == INT_MAX ? -1 : k1;
-    out.c[2] = k2 == INT_MAX ? -1 : k2;
-    out.c[3] = k3 == INT_MAX ? -1 : k3;
-    return count > 4;
+    return proj_candidates(F, q.cells, dMP, last_gate(F, u_right, q, mode),
+                           [frame_occ](int f) { return frame_occ[f] == 2; }, kLpThHigh, out);
 }
 
-// :1278-1283 is proj_rot_bin(LastFrame angle, CurrentFrame angle); ComputeThreeMaxima is proj_three_maxima.
-// The bins the removal of :1301-1311 spares, from the histogram over ALL claims
-RSCM_HD void last_keep_bins(const int* hs, int keep[3]) {
-    const int m = proj_three_maxima(hs, kProjHistoLength);
-    keep[0] = (m & 255) - 1;
-    keep[1] = ((m >> 8) & 255) - 1;
-    keep[2] = ((m >> 16) & 255) - 1;
+// What the rounds share, for LastFrame slot i: the window, the cache and an empty claim
+RSCM_HD void last_setup_slot(const LastProjProblem& Q, int i, float th) {
+    const DevProjFrame& F = *Q.F;
+    LpRec q = lp_no_window();
+    ProjCand cd = proj_no_cand();
+    if (last_eligible(Q.L, i)) {
+        q = last_setup(F, Q.mbf, Q.L, Q.Tcw, i, th);
+        if (q.cells >= 0 && last_candidates(F, Q.u_right, q, Q.L.mp_desc[i], Q.frame_occ, Q.mode, cd))
+            q.cells |= kProjMore;
+    }
+    Q.rec[i] = q;
+    Q.cand[i] = cd;
+    Q.claim[i] = -1;
 }
+
+// the matcher of the rounds (rsc_projrounds.h); lastproj.hip adds best_coop
+struct LastRounds {
+    static constexpr bool kCoopWalk = true;
+    const LastProjProblem& Q;
+    int mode;
+    RSCM_HD int n_points() const { return Q.L.n; }
+    RSCM_HD bool entry_occupied(int f) const { return Q.frame_occ[f] == 2; }
+    RSCM_HD bool blocks(int i) const { return Q.L.mp_has_obs[i] != 0; }  // :1248-1250
+    RSCM_HD int pick(int i, const int* owner) const {
+        const int cells = Q.rec[i].cells;
+        return cells < 0 ? kProjSkip : proj_pick(Q.cand[i], (cells & kProjMore) != 0, i, owner);
+    }
+    RSCM_HD int best(int i, const int* owner) const {  // :1242-1271
+        return last_best(*Q.F, Q.u_right, Q.rec[i], Q.L.mp_desc[i], i, owner, mode);
+    }
+};
+
+// :1278-1283 is proj_rot_bin(LastFrame angle, CurrentFrame angle).  The bins the removal of :1301-1311 spares,
+// from the histogram over ALL claims
+RSCM_HD void last_keep_bins(const int* hs, int keep[3]) { proj_keep_bins(hs, keep); }
 
 #if defined(__HIPCC__)
 // mid (may be NULL): recorded between the setup kernel and the rounds kernel.

@@ -11,23 +11,16 @@
 //
 //  1. Occupancy depends on the occupant (:58-60): feature f is skipped only when F.mvpMapPoints[f] is set
 //     AND that MapPoint has Observations() > 0.  A point without observations that takes f does not block
-//     the points after it: a later point may take f again and overwrite it, and both count in nmatches.
-//     The claimers of a feature, in point order, are therefore zero or more non-blocking points followed by
-//     at most one blocking point, so
-//         f is skipped by point i  <=>  min{ j : A[j] == f, has_obs[j] } < i
-//     with kProjOccupied for an entry occupant with observations (frame_occ == 2); an entry occupant without
-//     (frame_occ == 1) is free and is overwritten.  The owner table is built with atomicMin over the
-//     BLOCKING claimers only; the MapPoint left in mvpMapPoints[f] is the LAST claimer (atomicMax over all).
+//     the points after it: a later point may take f again and overwrite it, and both count in nmatches
+//     (the second owner rule of rsc_projcore.h).  An entry occupant with observations (frame_occ == 2)
+//     carries kProjOccupied; one without (frame_occ == 1) is free and is overwritten.  The MapPoint left in
+//     mvpMapPoints[f] is the LAST claimer (atomicMax over all claims).
 //  2. The decision is "best two free candidates, cutoff, ratio veto" (:73-92), not "first free minimum".
 //     An earlier point that takes i's best promotes the runner-up; one that takes i's RUNNER-UP can turn a
 //     vetoed match into an accepted one.
 //
-// Fixed point: one workgroup per (Frame, point list) problem iterates
-//     A[i] = lp_decide(best two of point i's candidates f with owner[f] >= i)
-// Point i reads only the claims of points j < i (owner[f] < i can only come from such a j), so point 0 is
-// final after round 1 and points 0..i after round i + 1: the fixed point is unique, equals the sequential
-// result and is reached in at most n_eligible + 1 rounds (the last one only confirms).  A plain bounded
-// loop: no cross-workgroup hand-off and nothing to wait for.
+// Mapping, visiting order and the fixed-point argument: rsc_projcore.h, with the owner rule "only claimers
+// with observations block" and A[i] = lp_decide(best two of point i's candidates f with owner[f] >= i).
 //
 // Candidate cache: the four smallest (distance, visiting order) candidates that pass the static gates
 // (window, levels, stereo, no entry occupant with observations) and have distance <= keep_max.  Unlike
@@ -39,7 +32,8 @@
 // leaves every decision unchanged.  When fewer than two cached candidates are free and the list was longer
 // than four, the point walks its window again: lp_best here, and on the device the same walk by 16 lanes
 // (lp_best_coop in localproj.hip: two smallest (distance, visiting rank) keys instead of the streaming
-// update, equal by the equivalence proved in tests/test_cpu_localproj.py).
+// update, equal by the equivalence proved in tests/test_cpu_localproj.py).  The finish leaves the LAST
+// claimer in out[f] and counts every claim.
 //
 // Precondition, as in rsc_frameproj.h: an eligible point whose u or v is NaN (camera z == 0 with x == 0 or
 // y == 0; the reference feeds NaN to floor there) is outside the reference's defined behaviour and is
@@ -144,14 +138,19 @@ RSCM_HD LpTrack lp_frustum(const DevProjFrame& F, float mbf, const DevKfpPoints&
     return t;
 }
 
-// ORBmatcher.cpp:31-40 and the cell range of GetFeaturesInArea (Frame.cpp:399-413).  The level of `t` must
-// be in [0, F.n_levels).
-RSCM_HD LpRec lp_window(const DevProjFrame& F, const LpTrack& t, float th) {
+RSCM_HD LpRec lp_no_window() {
     LpRec q;
     q.u = q.v = q.r = q.xr = 0.0f;
     q.cells = -1;
     q.in_view = 0;
     q.pad[0] = q.pad[1] = 0;
+    return q;
+}
+
+// ORBmatcher.cpp:31-40 and the cell range of GetFeaturesInArea (Frame.cpp:399-413).  The level of `t` must
+// be in [0, F.n_levels).
+RSCM_HD LpRec lp_window(const DevProjFrame& F, const LpTrack& t, float th) {
+    LpRec q = lp_no_window();
     if (!t.in_view) return q;                          // :25
     const float u = t.proj_x, v = t.proj_y;
     if (!(u == u) || !(v == v)) return q;              // the precondition above
@@ -163,35 +162,14 @@ RSCM_HD LpRec lp_window(const DevProjFrame& F, const LpTrack& t, float th) {
     q.v = v;
     q.r = rad;
     q.xr = t.proj_xr;
-    int x0 = (int)floorf((u - F.min_x - rad) * F.gw_inv);
-    if (x0 < 0) x0 = 0;
-    if (x0 >= kProjGridCols) return q;
-    int x1 = (int)ceilf((u - F.min_x + rad) * F.gw_inv);
-    if (x1 > kProjGridCols - 1) x1 = kProjGridCols - 1;
-    if (x1 < 0) return q;
-    int y0 = (int)floorf((v - F.min_y - rad) * F.gh_inv);
-    if (y0 < 0) y0 = 0;
-    if (y0 >= kProjGridRows) return q;
-    int y1 = (int)ceilf((v - F.min_y + rad) * F.gh_inv);
-    if (y1 > kProjGridRows - 1) y1 = kProjGridRows - 1;
-    if (y1 < 0) return q;
-    q.cells = x0 | x1 << 6 | y0 << 12 | y1 << 18 | t.level << 24;
+    q.cells = proj_cells(F, u, v, rad, t.level);
     return q;
 }
 
-// The gates of one (point, feature) pair that do not depend on the claims: levels [L-1, L] and the strict
-// window of GetFeaturesInArea (Frame.cpp:428-441), then the stereo gate (ORBmatcher.cpp:62-67)
-RSCM_HD bool lp_static_gate(const DevProjFrame& F, const float* u_right, const LpRec& q, int level, int f) {
-    const int oct = F.octave[f];
-    if (oct < level - 1 || oct > level) return false;
-    const ProjPt kp = F.kp[f];
-    if (!(fabsf(kp.x - q.u) < q.r && fabsf(kp.y - q.v) < q.r)) return false;
-    const float ur = u_right[f];
-    if (ur > 0.0f) {                                  // :62
-        const float er = fabsf(q.xr - ur);            // :64
-        if (er > q.r) return false;                   // :65, strict
-    }
-    return true;
+// the static gates of point q: levels [L-1, L], the window, then the stereo gate (ORBmatcher.cpp:62-67)
+RSCM_HD ProjStereoGate lp_gate(const DevProjFrame& F, const float* u_right, const LpRec& q) {
+    const int level = ProjCells(q.cells).level;
+    return ProjStereoGate{ProjGate(F, q.u, q.v, q.r, level - 1, level), u_right, q.xr};
 }
 
 // :47-51 and the streaming update of :73-85: equal to "the two smallest under (distance, visiting order)"
@@ -243,57 +221,17 @@ RSCM_HD int lp_keep_max(float nn_ratio) {
 // :54-95 over the window of `q`: the feature point i takes when the features with owner[f] < i are skipped
 // (an entry occupant with observations carries kProjOccupied), or -1
 template <class OwnerPtr>
-RSCM_HD int lp_best(const DevProjFrame& F, const float* u_right, const LpRec& q, const ProjDesc& dMP, int i,
+RSCM_HD int lp_best(const DevProjFrame& F, const float* u_right, const LpRec q, const ProjDesc dMP, int i,
                     OwnerPtr owner, float nn_ratio) {
     if (q.cells < 0) return -1;
-    const int x0 = q.cells & 63, x1 = (q.cells >> 6) & 63, y0 = (q.cells >> 12) & 63, y1 = (q.cells >> 18) & 63;
-    const int level = (q.cells >> 24) & 63;
+    const ProjStereoGate gate = lp_gate(F, u_right, q);
+    const ProjDesc* desc = F.desc;
     LpTop2 t = lp_top2_init();
-    for (int ix = x0; ix <= x1; ++ix)
-        for (int iy = y0; iy <= y1; ++iy) {
-            const int c = ix * kProjGridRows + iy;
-            const int e1 = F.cell_begin[c + 1];
-            for (int e = F.cell_begin[c]; e < e1; ++e) {
-                const int f = F.cell_feat[e];
-                if (!lp_static_gate(F, u_right, q, level, f)) continue;
-                if (owner[f] < i) continue;  // :58-60
-                lp_top2_push(t, proj_desc_dist(dMP, F.desc[f]), F.octave[f], f);
-            }
-        }
+    proj_walk(F, ProjCells(q.cells), [&](int f) {
+        if (!gate(f) || owner[f] < i) return;  // :58-60
+        lp_top2_push(t, proj_desc_dist(dMP, desc[f]), gate.g.octave[f], f);
+    });
     return lp_decide(t, nn_ratio);
-}
-
-// The walk of lp_best once, for all rounds: the four smallest (distance, visiting order) among the
-// candidates with distance <= keep_max on features without an entry occupant that has observations.
-// Returns true when more than four qualified.
-RSCM_HD bool lp_candidates(const DevProjFrame& F, const float* u_right, const LpRec& q, const ProjDesc& dMP,
-                           const uint8_t* frame_occ, int keep_max, ProjCand& out) {
-    const int x0 = q.cells & 63, x1 = (q.cells >> 6) & 63, y0 = (q.cells >> 12) & 63, y1 = (q.cells >> 18) & 63;
-    const int level = (q.cells >> 24) & 63;
-    int k0 = INT_MAX, k1 = INT_MAX, k2 = INT_MAX, k3 = INT_MAX, count = 0;
-    for (int ix = x0; ix <= x1; ++ix)
-        for (int iy = y0; iy <= y1; ++iy) {
-            const int c = ix * kProjGridRows + iy;
-            const int e1 = F.cell_begin[c + 1];
-            for (int e = F.cell_begin[c]; e < e1; ++e) {
-                const int f = F.cell_feat[e];
-                if (!lp_static_gate(F, u_right, q, level, f)) continue;
-                if (frame_occ[f] == 2) continue;
-                const int dist = proj_desc_dist(dMP, F.desc[f]);
-                if (dist > keep_max) continue;
-                ++count;
-                const int key = dist << 16 | f;  // a strict < keeps equal distances in visiting order
-                if (dist < (k0 >> 16)) { k3 = k2; k2 = k1; k1 = k0; k0 = key; }
-                else if (dist < (k1 >> 16)) { k3 = k2; k2 = k1; k1 = key; }
-                else if (dist < (k2 >> 16)) { k3 = k2; k2 = key; }
-                else if (dist < (k3 >> 16)) { k3 = key; }
-            }
-        }
-    out.c[0] = k0 == INT_MAX ? -1 : k0;
-    out.c[1] = k1 == INT_MAX ? -1 : k1;
-    out.c[2] = k2 == INT_MAX ? -1 : k2;
-    out.c[3] = k3 == INT_MAX ? -1 : k3;
-    return count > 4;
 }
 
 // One round's choice from the cached candidates: the feature, -1 for none, or -2 when fewer than two of
@@ -301,7 +239,7 @@ RSCM_HD bool lp_candidates(const DevProjFrame& F, const float* u_right, const Lp
 // of the candidates sorted by (distance, visiting order), so its first two free entries are the best and
 // the runner-up of the walk.
 template <class OwnerPtr>
-RSCM_HD int lp_pick(const DevProjFrame& F, const ProjCand& cd, bool more, int i, OwnerPtr owner, float nn_ratio) {
+RSCM_HD int lp_pick(const DevProjFrame& F, const ProjCand cd, bool more, int i, OwnerPtr owner, float nn_ratio) {
     LpTop2 t = lp_top2_init();
     int found = 0;
     bool complete = !more;
@@ -321,6 +259,52 @@ RSCM_HD int lp_pick(const DevProjFrame& F, const ProjCand& cd, bool more, int i,
     if (found < 2 && !complete) return -2;
     return lp_decide(t, nn_ratio);
 }
+
+// the cache of point q: distance <= keep_max on features without an entry occupant that has observations; true
+// when more than four qualified
+RSCM_HD bool lp_candidates(const DevProjFrame& F, const float* u_right, const LpRec& q, const ProjDesc& dMP,
+                           const uint8_t* frame_occ, int keep_max, ProjCand& out) {
+    return proj_candidates(F, q.cells, dMP, lp_gate(F, u_right, q), [frame_occ](int f) { return frame_occ[f] == 2; },
+                           keep_max, out);
+}
+
+// What the rounds share, for point i: isInFrustum (fused: its record goes to the caller-visible `track`; else
+// the caller's record is read from there), the window, the cache and an empty claim
+RSCM_HD void lp_setup_point(const LocalProjProblem& Q, int i, int fused, float cos_limit, float th, int keep_max) {
+    const DevProjFrame& F = *Q.F;
+    LpTrack t = lp_not_in_view();
+    const bool eligible = lp_eligible(Q.P, Q.skip, i);
+    if (fused) {
+        if (eligible) t = lp_frustum(F, Q.mbf, Q.P, Q.Tcw, i, cos_limit);
+        Q.track[i] = t;
+    } else if (eligible) {
+        t = Q.track[i];
+        if ((unsigned)t.level >= (unsigned)F.n_levels) t.in_view = 0;  // the host checked it; never index past scale[]
+    }
+    LpRec q = lp_window(F, t, th);
+    ProjCand cd = proj_no_cand();
+    if (q.cells >= 0 && lp_candidates(F, Q.u_right, q, Q.P.desc[i], Q.frame_occ, keep_max, cd)) q.cells |= kProjMore;
+    Q.rec[i] = q;
+    Q.cand[i] = cd;
+    Q.claim[i] = -1;
+}
+
+// the matcher of the rounds (rsc_projrounds.h); localproj.hip adds best_coop
+struct LpRounds {
+    static constexpr bool kCoopWalk = true;
+    const LocalProjProblem& Q;
+    float nn_ratio;
+    RSCM_HD int n_points() const { return Q.P.n; }
+    RSCM_HD bool entry_occupied(int f) const { return Q.frame_occ[f] == 2; }
+    RSCM_HD bool blocks(int i) const { return Q.has_obs[i] != 0; }  // a point without observations blocks nobody
+    RSCM_HD int pick(int i, const int* owner) const {
+        const int cells = Q.rec[i].cells;
+        return cells < 0 ? kProjSkip : lp_pick(*Q.F, Q.cand[i], (cells & kProjMore) != 0, i, owner, nn_ratio);
+    }
+    RSCM_HD int best(int i, const int* owner) const {
+        return lp_best(*Q.F, Q.u_right, Q.rec[i], Q.P.desc[i], i, owner, nn_ratio);
+    }
+};
 
 #if defined(__HIPCC__)
 // fused != 0: the setup kernel runs isInFrustum and writes `track`; else it reads `track`.  mid (may be

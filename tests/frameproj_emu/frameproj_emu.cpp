@@ -6,6 +6,7 @@
 #include <cstring>
 #include <vector>
 #include "../../orb-slam2-optimized_amd/csrc/rsc_frameproj.h"
+#include "../proj_emu_common.h"
 
 using namespace rsc;
 
@@ -43,23 +44,14 @@ struct fpe_problem {
 
 namespace {
 
-struct Views {
-    DevProjFrame F;
+struct Views : EmuFrame {
     DevProjKF K;
-    std::vector<ProjDesc> fdesc, kdesc;  // aligned copies
-    std::vector<ProjPt> kp;
+    std::vector<ProjDesc> kdesc;  // aligned copy
 };
 
 void make_views(const fpe_problem& p, Views& v) {
-    v.fdesc.resize((size_t)p.nf + 1);
-    v.kdesc.resize((size_t)p.nk + 1);
-    v.kp.resize((size_t)p.nf + 1);
-    if (p.nf) std::memcpy(v.fdesc.data(), p.desc, 32 * (size_t)p.nf);
-    if (p.nk) std::memcpy(v.kdesc.data(), p.mp_desc, 32 * (size_t)p.nk);
-    if (p.nf) std::memcpy(v.kp.data(), p.kp, 8 * (size_t)p.nf);
-    v.F = DevProjFrame{v.kp.data(), p.octave, p.angle, v.fdesc.data(), p.cell_begin, p.cell_feat, p.scale,
-                       p.min_x, p.max_x, p.min_y, p.max_y, p.gw_inv, p.gh_inv, p.fx, p.fy, p.cx, p.cy, p.log_sf,
-                       p.nf, p.n_levels};
+    make_frame_view(p, p.nf, p.angle, v);
+    v.kdesc = emu_aligned_descs(p.mp_desc, p.nk);
     v.K = DevProjKF{p.mp_state, p.mp_pos, p.mp_dmax, p.mp_dmin, v.kdesc.data(), p.kf_angle, p.nk};
 }
 
@@ -74,10 +66,7 @@ int finish(const fpe_problem& p, const Views& v, const std::vector<int>& claim, 
                 const int b = proj_rot_bin(v.K.angle[i], v.F.angle[claim[i]]);
                 if ((unsigned)b < (unsigned)kProjHistoLength) ++hist[b];
             }
-        const int m = proj_three_maxima(hist, kProjHistoLength);
-        keep[0] = (m & 255) - 1;
-        keep[1] = ((m >> 8) & 255) - 1;
-        keep[2] = ((m >> 16) & 255) - 1;
+        proj_keep_bins(hist, keep);
     }
     int n = 0;
     for (int i = 0; i < p.nk; ++i) {
@@ -113,44 +102,31 @@ int fpe_search_sequential(const fpe_problem* p, int32_t* out) {
     return finish(*p, v, claim, out);
 }
 
-// The kernels' work (frameproj.hip): the windows and the four best candidates of every MapPoint once,
-// then rounds that rebuild the owner table from the claims of the round before and recompute every
-// MapPoint against it (from the cached candidates, or by walking the window when they are all taken and
-// there were more).  Returns nmatches; *rounds = rounds run.
+// The kernels' work (frameproj.hip): proj_setup_point for every MapPoint, then the rounds.  Returns nmatches;
+// *rounds = rounds run.
 int fpe_search_fixed_point(const fpe_problem* p, int32_t* out, int32_t* rounds) {
     Views v;
     make_views(*p, v);
-    std::vector<int> owner((size_t)p->nf + 1), claim((size_t)p->nk + 1, -1), next((size_t)p->nk + 1, -1);
+    std::vector<int> claim((size_t)p->nk + 1);
     std::vector<ProjRec> rec((size_t)p->nk + 1);
     std::vector<ProjCand> cand((size_t)p->nk + 1);
+    FrameProjProblem P{};
+    P.F = &v.F;
+    P.K = v.K;
+    std::memcpy(P.Tcw, p->Tcw, 12 * sizeof(float));
+    P.already = p->already;
+    P.frame_mp = p->frame_mp;
+    P.rec = rec.data();
+    P.cand = cand.data();
+    P.claim = claim.data();
     int n_eligible = 0;  // the MapPoints with a window
     for (int i = 0; i < p->nk; ++i) {
-        rec[i] = proj_eligible(v.K, p->already, i) ? proj_setup(v.F, v.K, p->Tcw, i, p->th) : proj_no_window();
-        cand[i].c[0] = cand[i].c[1] = cand[i].c[2] = cand[i].c[3] = -1;
-        if (rec[i].cells < 0) continue;
-        ++n_eligible;
-        if (proj_candidates(v.F, rec[i], v.K.mp_desc[i], p->frame_mp, p->orb_dist, cand[i])) rec[i].cells |= kProjMore;
+        proj_setup_point(P, i, p->th, p->orb_dist);
+        n_eligible += rec[i].cells >= 0;
     }
-    int done = 0;
-    for (int r = 0; r < n_eligible + 1; ++r) {
-        for (int f = 0; f < p->nf; ++f) owner[f] = p->frame_mp[f] >= 0 ? kProjOccupied : kProjFree;
-        for (int i = 0; i < p->nk; ++i)
-            if (claim[i] >= 0 && i < owner[claim[i]]) owner[claim[i]] = i;  // atomicMin
-        bool changed = false;
-        for (int i = 0; i < p->nk; ++i) {
-            int b = -1;
-            if (rec[i].cells >= 0) {
-                b = proj_pick(cand[i], (rec[i].cells & kProjMore) != 0, i, owner.data());
-                if (b == -2) b = proj_best(v.F, rec[i], v.K.mp_desc[i], i, owner.data(), p->orb_dist);
-            }
-            next[i] = b;
-            changed |= next[i] != claim[i];
-        }
-        claim.swap(next);
-        ++done;
-        if (!changed) break;
-    }
-    *rounds = done;
+    const int32_t* frame_mp = p->frame_mp;
+    const auto occ = [frame_mp](int f) { return frame_mp[f] >= 0; };
+    *rounds = emu_rounds(FrameRounds<decltype(occ)>{P, p->orb_dist, occ}, p->nf, P.claim, n_eligible, nullptr);
     return finish(*p, v, claim, out);
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../orb-slam2-optimized_amd/csrc/rsc_kfproj.h"
 #include "../../orb-slam2-optimized_amd/csrc/rsc_sim3compose.h"
+#include "../proj_emu_common.h"
 
 using namespace rsc;
 
@@ -46,22 +47,16 @@ struct kfpe_problem {
 namespace {
 
 struct Views {
+    EmuFrame k;
     DevKfpKF K;
     DevKfpPoints P;
-    std::vector<ProjDesc> kdesc, pdesc;  // aligned copies
-    std::vector<ProjPt> kp;
+    std::vector<ProjDesc> pdesc;  // aligned copy
 };
 
 void make_views(const kfpe_problem& p, Views& v) {
-    v.kdesc.resize((size_t)p.nk + 1);
-    v.pdesc.resize((size_t)p.np + 1);
-    v.kp.resize((size_t)p.nk + 1);
-    if (p.nk) std::memcpy(v.kdesc.data(), p.desc, 32 * (size_t)p.nk);
-    if (p.np) std::memcpy(v.pdesc.data(), p.pdesc, 32 * (size_t)p.np);
-    if (p.nk) std::memcpy(v.kp.data(), p.kp, 8 * (size_t)p.nk);
-    v.K = DevKfpKF{v.kp.data(), p.octave, v.kdesc.data(), p.cell_begin, p.cell_feat, p.scale,
-                   p.min_x, p.max_x, p.min_y, p.max_y, p.gw_inv, p.gh_inv, p.fx, p.fy, p.cx, p.cy, p.log_sf,
-                   p.nk, p.n_levels};
+    make_frame_view(p, p.nk, nullptr, v.k);
+    static_cast<DevProjFrame&>(v.K) = v.k.F;
+    v.pdesc = emu_aligned_descs(p.pdesc, p.np);
     v.P = DevKfpPoints{p.state, p.pos, p.normal, p.dmax, p.dmin, v.pdesc.data(), p.np};
 }
 
@@ -98,49 +93,29 @@ int kfpe_search_sequential(const kfpe_problem* p, int32_t* out) {
     return finish(*p, claim, out);
 }
 
-// The kernels' work (kfproj.hip): the windows and the four best candidates of every point once, then rounds
-// that rebuild the owner table from the claims of the round before and recompute every point against it.
-// Returns nmatches; *rounds = rounds run; *fallbacks = window walks taken because the cached four were gone.
+// The kernels' work (kfproj.hip): kfp_setup_point for every point, then the rounds.  Returns nmatches;
+// *rounds = rounds run; *fallbacks = window walks taken because the cached four were gone.
 int kfpe_search_fixed_point(const kfpe_problem* p, int32_t* out, int32_t* rounds, int32_t* fallbacks) {
     Views v;
     make_views(*p, v);
-    float R[9], t[3];
-    kfp_decompose(p->Scw, false, R, t);
-    std::vector<int> owner((size_t)p->nk + 1), claim((size_t)p->np + 1, -1), next((size_t)p->np + 1, -1);
+    std::vector<int> claim((size_t)p->np + 1);
     std::vector<ProjRec> rec((size_t)p->np + 1);
     std::vector<ProjCand> cand((size_t)p->np + 1);
-    int n_eligible = 0, walks = 0;
+    KfProjProblem Q{};
+    Q.K = v.K;
+    Q.P = v.P;
+    std::memcpy(Q.Scw, p->Scw, 12 * sizeof(float));
+    Q.already = p->skip;
+    Q.occupied = p->occupied;
+    Q.rec = rec.data();
+    Q.cand = cand.data();
+    Q.claim = claim.data();
+    int n_eligible = 0;
     for (int i = 0; i < p->np; ++i) {
-        rec[i] = kfp_eligible(v.P, p->skip, i) ? kfp_setup(v.K, v.P, R, t, i, p->th, false) : proj_no_window();
-        cand[i].c[0] = cand[i].c[1] = cand[i].c[2] = cand[i].c[3] = -1;
-        if (rec[i].cells < 0) continue;
-        ++n_eligible;
-        if (kfp_candidates(v.K, rec[i], v.P.desc[i], p->occupied, cand[i])) rec[i].cells |= kProjMore;
+        kfp_setup_point(Q, i, p->th);
+        n_eligible += rec[i].cells >= 0;
     }
-    int done = 0;
-    for (int r = 0; r < n_eligible + 1; ++r) {
-        for (int f = 0; f < p->nk; ++f) owner[f] = p->occupied[f] ? kProjOccupied : kProjFree;
-        for (int i = 0; i < p->np; ++i)
-            if (claim[i] >= 0 && i < owner[claim[i]]) owner[claim[i]] = i;  // atomicMin
-        bool changed = false;
-        for (int i = 0; i < p->np; ++i) {
-            int b = -1;
-            if (rec[i].cells >= 0) {
-                b = proj_pick(cand[i], (rec[i].cells & kProjMore) != 0, i, owner.data());
-                if (b == -2) {
-                    b = kfp_best(v.K, rec[i], v.P.desc[i], i, owner.data());
-                    ++walks;
-                }
-            }
-            next[i] = b;
-            changed |= next[i] != claim[i];
-        }
-        claim.swap(next);
-        ++done;
-        if (!changed) break;
-    }
-    *rounds = done;
-    if (fallbacks) *fallbacks = walks;
+    *rounds = emu_rounds(KfpRounds{Q}, p->nk, Q.claim, n_eligible, fallbacks);
     return finish(*p, claim, out);
 }
 

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "../../orb-slam2-optimized_amd/csrc/rsc_lastproj.h"
+#include "../proj_emu_common.h"
 
 using namespace rsc;
 
@@ -50,34 +51,15 @@ struct lse_problem {
 
 namespace {
 
-struct Views {
-    DevProjFrame F;
+struct Views : EmuFrame {
     DevLastFrame L;
-    std::vector<ProjDesc> fdesc, ldesc;  // aligned copies
-    std::vector<ProjPt> kp;
+    std::vector<ProjDesc> ldesc;  // aligned copy
 };
 
 void make_views(const lse_problem& p, Views& v) {
-    v.fdesc.resize((size_t)p.nf + 1);
-    v.ldesc.resize((size_t)p.nl + 1);
-    v.kp.resize((size_t)p.nf + 1);
-    if (p.nf) std::memcpy(v.fdesc.data(), p.desc, 32 * (size_t)p.nf);
-    if (p.nl) std::memcpy(v.ldesc.data(), p.mp_desc, 32 * (size_t)p.nl);
-    if (p.nf) std::memcpy(v.kp.data(), p.kp, 8 * (size_t)p.nf);
-    v.F = DevProjFrame{v.kp.data(), p.octave, p.angle, v.fdesc.data(), p.cell_begin, p.cell_feat, p.scale,
-                       p.min_x, p.max_x, p.min_y, p.max_y, p.gw_inv, p.gh_inv, p.fx, p.fy, p.cx, p.cy, p.log_sf,
-                       p.nf, p.n_levels};
+    make_frame_view(p, p.nf, p.angle, v);
+    v.ldesc = emu_aligned_descs(p.mp_desc, p.nl);
     v.L = DevLastFrame{p.l_octave, p.l_angle, p.mp_state, p.mp_pos, v.ldesc.data(), p.mp_has_obs, p.nl};
-}
-
-LpRec setup_slot(const lse_problem& p, const Views& v, int i) {
-    LpRec q;
-    q.u = q.v = q.r = q.xr = 0.0f;
-    q.cells = -1;
-    q.in_view = 0;
-    q.pad[0] = q.pad[1] = 0;
-    if (last_eligible(v.L, i)) q = last_setup(v.F, p.mbf, v.L, p.Tcw_cur, i, p.th);
-    return q;
 }
 
 }  // namespace
@@ -101,7 +83,7 @@ void lse_search_sequential(const lse_problem* p, int32_t* out, int32_t* counts) 
     }
     int nmatches = 0, claims = 0;
     for (int i = 0; i < p->nl; ++i) {
-        const LpRec q = setup_slot(*p, v, i);
+        const LpRec q = last_eligible(v.L, i) ? last_setup(v.F, p->mbf, v.L, p->Tcw_cur, i, p->th) : lp_no_window();
         const int b = last_best(v.F, p->u_right, q, v.L.mp_desc[i], i, owner.data(), mode);
         if (b < 0) continue;
         mp[b] = i;                                                       // :1273
@@ -133,48 +115,33 @@ void lse_search_sequential(const lse_problem* p, int32_t* out, int32_t* counts) 
     counts[3] = claims;
 }
 
-// The kernels' work (lastproj.hip): the windows and the cached candidates of every slot once, then rounds
-// that rebuild the owner table from the blocking claims of the round before and recompute every slot against
-// it, then the histogram over all claims, the last-writer table and the nulling.  counts = nmatches, mode,
-// rounds, claims; *fallbacks = window walks taken.
+// The kernels' work (lastproj.hip): last_setup_slot for every slot, then the rounds, then the histogram over
+// all claims, the last-writer table and the nulling.  counts = nmatches, mode, rounds, claims; *fallbacks =
+// window walks taken.
 void lse_search_fixed_point(const lse_problem* p, int32_t* out, int32_t* counts, int32_t* fallbacks) {
     Views v;
     make_views(*p, v);
     const int mode = last_mode(p->Tcw_cur, p->Tcw_last, p->mb);
-    std::vector<int> owner((size_t)p->nf + 1), claim((size_t)p->nl + 1, -1), next((size_t)p->nl + 1, -1);
+    std::vector<int> claim((size_t)p->nl + 1);
     std::vector<LpRec> rec((size_t)p->nl + 1);
     std::vector<ProjCand> cand((size_t)p->nl + 1);
-    int n_eligible = 0, walks = 0;
+    LastProjProblem Q{};
+    Q.F = &v.F;
+    Q.u_right = p->u_right;
+    Q.mbf = p->mbf;
+    Q.mode = mode;
+    Q.L = v.L;
+    std::memcpy(Q.Tcw, p->Tcw_cur, 12 * sizeof(float));
+    Q.frame_occ = p->frame_occ;
+    Q.rec = rec.data();
+    Q.cand = cand.data();
+    Q.claim = claim.data();
+    int n_eligible = 0;
     for (int i = 0; i < p->nl; ++i) {
-        rec[i] = setup_slot(*p, v, i);
-        cand[i].c[0] = cand[i].c[1] = cand[i].c[2] = cand[i].c[3] = -1;
-        if (rec[i].cells < 0) continue;
-        ++n_eligible;
-        if (last_candidates(v.F, p->u_right, rec[i], v.L.mp_desc[i], p->frame_occ, mode, cand[i]))
-            rec[i].cells |= kProjMore;
+        last_setup_slot(Q, i, p->th);
+        n_eligible += rec[i].cells >= 0;
     }
-    int done = 0;
-    for (int r = 0; r < n_eligible + 1; ++r) {
-        for (int f = 0; f < p->nf; ++f) owner[f] = p->frame_occ[f] == 2 ? kProjOccupied : kProjFree;
-        for (int i = 0; i < p->nl; ++i)
-            if (claim[i] >= 0 && p->mp_has_obs[i] && i < owner[claim[i]]) owner[claim[i]] = i;  // atomicMin
-        bool changed = false;
-        for (int i = 0; i < p->nl; ++i) {
-            int b = -1;
-            if (rec[i].cells >= 0) {
-                b = proj_pick(cand[i], (rec[i].cells & kProjMore) != 0, i, owner.data());
-                if (b == -2) {
-                    b = last_best(v.F, p->u_right, rec[i], v.L.mp_desc[i], i, owner.data(), mode);
-                    ++walks;
-                }
-            }
-            next[i] = b;
-            changed |= next[i] != claim[i];
-        }
-        claim.swap(next);
-        ++done;
-        if (!changed) break;
-    }
+    const int done = emu_rounds(LastRounds{Q, mode}, p->nf, Q.claim, n_eligible, fallbacks);
     int hs[kProjHistoLength] = {}, keep[3] = {-1, -1, -1};
     if (p->check_ori) {
         for (int i = 0; i < p->nl; ++i) {
@@ -206,7 +173,6 @@ void lse_search_fixed_point(const lse_problem* p, int32_t* out, int32_t* counts,
     counts[1] = mode;
     counts[2] = done;
     counts[3] = total;
-    if (fallbacks) *fallbacks = walks;
 }
 
 }  // extern "C"

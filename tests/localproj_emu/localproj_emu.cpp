@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 #include "../../orb-slam2-optimized_amd/csrc/rsc_localproj.h"
+#include "../proj_emu_common.h"
 
 using namespace rsc;
 
@@ -49,23 +50,14 @@ struct lpe_problem {
 
 namespace {
 
-struct Views {
-    DevProjFrame F;
+struct Views : EmuFrame {
     DevKfpPoints P;
-    std::vector<ProjDesc> fdesc, pdesc;  // aligned copies
-    std::vector<ProjPt> kp;
+    std::vector<ProjDesc> pdesc;  // aligned copy
 };
 
 void make_views(const lpe_problem& p, Views& v) {
-    v.fdesc.resize((size_t)p.nf + 1);
-    v.pdesc.resize((size_t)p.np + 1);
-    v.kp.resize((size_t)p.nf + 1);
-    if (p.nf) std::memcpy(v.fdesc.data(), p.desc, 32 * (size_t)p.nf);
-    if (p.np) std::memcpy(v.pdesc.data(), p.pdesc, 32 * (size_t)p.np);
-    if (p.nf) std::memcpy(v.kp.data(), p.kp, 8 * (size_t)p.nf);
-    v.F = DevProjFrame{v.kp.data(), p.octave, nullptr, v.fdesc.data(), p.cell_begin, p.cell_feat, p.scale,
-                       p.min_x, p.max_x, p.min_y, p.max_y, p.gw_inv, p.gh_inv, p.fx, p.fy, p.cx, p.cy, p.log_sf,
-                       p.nf, p.n_levels};
+    make_frame_view(p, p.nf, nullptr, v);
+    v.pdesc = emu_aligned_descs(p.pdesc, p.np);
     v.P = DevKfpPoints{p.state, p.pos, p.normal, p.dmax, p.dmin, v.pdesc.data(), p.np};
 }
 
@@ -125,52 +117,38 @@ void lpe_search_sequential(const lpe_problem* p, int32_t* out, LpTrack* track, i
     counts[2] = 0;
 }
 
-// The kernels' work (localproj.hip): the windows and the cached candidates of every point once, then rounds
-// that rebuild the owner table from the blocking claims of the round before and recompute every point
-// against it.  counts = nmatches, nToMatch, rounds; *fallbacks = window walks taken.
+// The kernels' work (localproj.hip): lp_setup_point for every point, then the rounds.  counts = nmatches,
+// nToMatch, rounds; *fallbacks = window walks taken.
 void lpe_search_fixed_point(const lpe_problem* p, int32_t* out, LpTrack* track, int32_t* counts, int32_t* fallbacks) {
     Views v;
     make_views(*p, v);
-    std::vector<int> owner((size_t)p->nf + 1), claim((size_t)p->np + 1, -1), next((size_t)p->np + 1, -1);
+    std::vector<int> claim((size_t)p->np + 1);
     std::vector<LpRec> rec((size_t)p->np + 1);
     std::vector<ProjCand> cand((size_t)p->np + 1);
+    LocalProjProblem Q{};
+    Q.F = &v.F;
+    Q.u_right = p->u_right;
+    Q.mbf = p->mbf;
+    Q.P = v.P;
+    if (p->fused) std::memcpy(Q.Tcw, p->Tcw, 12 * sizeof(float));
+    Q.skip = p->skip;
+    Q.has_obs = p->has_obs;
+    Q.frame_occ = p->frame_occ;
+    Q.track = track;  // matcher-only mode reads the caller's records from there
+    Q.rec = rec.data();
+    Q.cand = cand.data();
+    Q.claim = claim.data();
+    if (!p->fused && p->np) std::memmove(track, p->track_in, sizeof(LpTrack) * (size_t)p->np);
     const int keep_max = lp_keep_max(p->nn_ratio);
-    int n_eligible = 0, n_to_match = 0, walks = 0;
+    int n_eligible = 0, n_to_match = 0;
     for (int i = 0; i < p->np; ++i) {
-        rec[i] = setup_point(*p, v, i, &track[i]);
+        lp_setup_point(Q, i, p->fused, p->cos_limit, p->th, keep_max);
         n_to_match += rec[i].in_view;
-        cand[i].c[0] = cand[i].c[1] = cand[i].c[2] = cand[i].c[3] = -1;
-        if (rec[i].cells < 0) continue;
-        ++n_eligible;
-        if (lp_candidates(v.F, p->u_right, rec[i], v.P.desc[i], p->frame_occ, keep_max, cand[i]))
-            rec[i].cells |= kProjMore;
+        n_eligible += rec[i].cells >= 0;
     }
-    int done = 0;
-    for (int r = 0; r < n_eligible + 1; ++r) {
-        for (int f = 0; f < p->nf; ++f) owner[f] = p->frame_occ[f] == 2 ? kProjOccupied : kProjFree;
-        for (int i = 0; i < p->np; ++i)
-            if (claim[i] >= 0 && p->has_obs[i] && i < owner[claim[i]]) owner[claim[i]] = i;  // atomicMin
-        bool changed = false;
-        for (int i = 0; i < p->np; ++i) {
-            int b = -1;
-            if (rec[i].cells >= 0) {
-                b = lp_pick(v.F, cand[i], (rec[i].cells & kProjMore) != 0, i, owner.data(), p->nn_ratio);
-                if (b == -2) {
-                    b = lp_best(v.F, p->u_right, rec[i], v.P.desc[i], i, owner.data(), p->nn_ratio);
-                    ++walks;
-                }
-            }
-            next[i] = b;
-            changed |= next[i] != claim[i];
-        }
-        claim.swap(next);
-        ++done;
-        if (!changed) break;
-    }
+    counts[2] = emu_rounds(LpRounds{Q, p->nn_ratio}, p->nf, Q.claim, n_eligible, fallbacks);
     counts[0] = finish(*p, claim, out);
     counts[1] = n_to_match;
-    counts[2] = done;
-    if (fallbacks) *fallbacks = walks;
 }
 
 // the streaming update of ORBmatcher.cpp:73-85 over a sequence: res = bestDist, bestLevel, bestDist2,
