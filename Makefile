@@ -11,7 +11,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
-     facade_lastproj_test
+     facade_lastproj_test arena_test
 
 OBJS = $(addprefix $(LIBDIR)/,kernels.o mlpnp.o poseopt.o sim3opt.o orbmatch.o sim3match.o frameproj.o kfproj.o \
          localproj.o lastproj.o kfdb.o bowvoc.o rsc_api.o)
@@ -58,6 +58,18 @@ $(LIBDIR)/chase_mirror_test_san: tests/cpp/chase_mirror_test.cpp $(CSRC)/rsc_cor
 	mkdir -p $(LIBDIR)
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
 
+# TEST-ONLY host programs: the staging-arena cursor against the matchers' former offset arithmetic
+# (tests/test_cpu_arena.py); the second build runs under the host sanitizers
+arena_test: $(LIBDIR)/arena_test $(LIBDIR)/arena_test_san
+
+$(LIBDIR)/arena_test: tests/cpp/arena_test.cpp $(CSRC)/rsc_arena.h
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/arena_test_san: tests/cpp/arena_test.cpp $(CSRC)/rsc_arena.h
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -84,4 +96,4 @@ clean:
 	       tests/localproj_emu/build tests/lastproj_emu/build
 
 .PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu facade_localproj_test facade_lastproj_test facade_test facade_proj_test facade_loopproj_test \
-        facade_voc_test chase_mirror_test clean
+        facade_voc_test chase_mirror_test arena_test clean

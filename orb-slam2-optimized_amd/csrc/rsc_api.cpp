@@ -18,6 +18,7 @@
 #include <vector>
 #include <memory>
 #include "../../include/rsc.h"
+#include "rsc_arena.h"
 #include "rsc_kernels.h"
 #include "rsc_engine.h"
 #include "rsc_poseopt.h"
@@ -477,6 +478,52 @@ void host_mark(rsc_context* C, int k) {
 
 void timing_begin(rsc_context* C, int slot) {
     if (C->timing) (void)hipEventRecord(C->ev[slot], C->stream);
+}
+
+// The timed launch of the batched entry points: ev[3] and ev[4] around it, read by timing_read after
+// the call's synchronise.
+template <class Launch>
+hipError_t timed_launch(rsc_context* C, Launch&& launch) {
+    timing_begin(C, 3);
+    const hipError_t e = launch();
+    if (e == hipSuccess) timing_begin(C, 4);
+    return e;
+}
+
+// rsc_context_last_kernel_timing: [2] the launch; with `mid` (the launch recorded ev[5] between its two
+// kernels) also [0] setup kernel, [1] rounds kernel
+void timing_read(rsc_context* C, bool mid = false) {
+    if (!C->timing) return;
+    float ms[3] = {0, 0, 0};
+    (void)hipEventElapsedTime(&ms[2], C->ev[3], C->ev[4]);
+    if (mid) {
+        (void)hipEventElapsedTime(&ms[0], C->ev[3], C->ev[5]);
+        (void)hipEventElapsedTime(&ms[1], C->ev[5], C->ev[4]);
+    }
+    for (int i = mid ? 0 : 2; i < 3; ++i) C->last_ms[i] = ms[i];
+}
+
+// One batched call over a staging arena (rsc_arena.h): fill(h, d) writes the problem table and the
+// inputs into the pinned mirror h (d: the device addresses the table points at) and may refuse the call
+// with a status; launch(d) enqueues the kernels.  `download` false: nothing comes back; `mid`: see
+// timing_read.  Returns with the outputs in the mirror, [A.back, A.bytes).
+template <class Fill, class Launch>
+int arena_run(rsc_context* C, DevBuf<char>& dev, PinBuf<char>& pin, const Arena& A, Fill&& fill, Launch&& launch,
+              bool download = true, bool mid = false) {
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = dev.ensure(A.bytes)) return e;
+    if (int e = pin.ensure(A.bytes)) return e;
+    // the previous call's copies into and out of the pinned mirror must be complete before it is rewritten
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    char* h = pin.p;
+    char* d = dev.p;
+    if (int e = fill(h, d)) return e;
+    RSC_HIP(hipMemcpyAsync(d, h, A.up, hipMemcpyHostToDevice, C->stream));
+    RSC_HIP(timed_launch(C, [&] { return launch(d); }));
+    if (download) RSC_HIP(hipMemcpyAsync(h + A.back, d + A.back, A.bytes - A.back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    timing_read(C, mid);
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1829,12 +1876,11 @@ int rsc_pose_optimization_many(rsc_context* C, const rsc_poseopt_problem* P, int
     if (R == 0) return RSC_OK;
     const size_t E = eoff.back();
     RSC_HIP(hipSetDevice(C->device));
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_probs = 0, o_xw = al(sizeof(DevPoseProb) * R), o_uv = o_xw + al(sizeof(float4) * E);
-    const size_t o_ur = o_uv + al(sizeof(float2) * E);  // mvuRight of the edges (stereo: >= 0)
-    const size_t in_bytes = o_ur + al(sizeof(float) * E);
-    const size_t r_out = 0, r_flags = al(sizeof(float) * 16 * R);
-    const size_t res_bytes = r_flags + al(E);
+    const size_t o_probs = 0, o_xw = al256(sizeof(DevPoseProb) * R), o_uv = o_xw + al256(sizeof(float4) * E);
+    const size_t o_ur = o_uv + al256(sizeof(float2) * E);  // mvuRight of the edges (stereo: >= 0)
+    const size_t in_bytes = o_ur + al256(sizeof(float) * E);
+    const size_t r_out = 0, r_flags = al256(sizeof(float) * 16 * R);
+    const size_t res_bytes = r_flags + al256(E);
     if (int e = C->h_po_in.ensure(in_bytes)) return e;
     if (int e = C->d_po_in.ensure(in_bytes)) return e;
     if (int e = C->h_po_res.ensure(res_bytes)) return e;
@@ -1870,17 +1916,13 @@ int rsc_pose_optimization_many(rsc_context* C, const rsc_poseopt_problem* P, int
         for (int j = 0; j < 12; ++j) dp.T[j] = q.Tcw[j];
     }
     RSC_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_poseopt(R, reinterpret_cast<const DevPoseProb*>(d + o_probs), C->h_flag + kFaultWord, C->stream));
-    timing_begin(C, 4);
+    RSC_HIP(timed_launch(C, [&] {
+        return launch_poseopt(R, reinterpret_cast<const DevPoseProb*>(d + o_probs), C->h_flag + kFaultWord, C->stream);
+    }));
     RSC_HIP(hipMemcpyAsync(C->h_po_res.p, C->d_po_res.p, res_bytes, hipMemcpyDeviceToHost, C->stream));
     RSC_HIP(hipStreamSynchronize(C->stream));
     if (int e = take_fault(C)) return e;
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+    timing_read(C);
     const float* ho = reinterpret_cast<const float*>(C->h_po_res.p + r_out);
     const uint8_t* hf = reinterpret_cast<const uint8_t*>(C->h_po_res.p + r_flags);
     for (int k = 0; k < R; ++k) {
@@ -1938,10 +1980,9 @@ int rsc_optimize_sim3_many(rsc_context* C, const rsc_sim3opt_problem* P, int cou
     if (R == 0) return RSC_OK;
     const size_t M = moff.back();
     RSC_HIP(hipSetDevice(C->device));
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_e12 = al(sizeof(DevSim3OptProb) * R), o_e21 = o_e12 + al(sizeof(float4) * M);
-    const size_t o_uv = o_e21 + al(sizeof(float4) * M), in_bytes = o_uv + al(sizeof(float4) * M);
-    const size_t r_keep = al(sizeof(double) * 16 * R), res_bytes = r_keep + al(M);
+    const size_t o_e12 = al256(sizeof(DevSim3OptProb) * R), o_e21 = o_e12 + al256(sizeof(float4) * M);
+    const size_t o_uv = o_e21 + al256(sizeof(float4) * M), in_bytes = o_uv + al256(sizeof(float4) * M);
+    const size_t r_keep = al256(sizeof(double) * 16 * R), res_bytes = r_keep + al256(M);
     if (int e = C->h_so_in.ensure(in_bytes)) return e;
     if (int e = C->d_so_in.ensure(in_bytes)) return e;
     if (int e = C->h_so_res.ensure(res_bytes)) return e;
@@ -1995,8 +2036,8 @@ int rsc_optimize_sim3_many(rsc_context* C, const rsc_sim3opt_problem* P, int cou
         hp[k].clist = nullptr;
     }
     if (helpers > 0) {
-        const size_t o_pub = al(sizeof(SoCoopFlags) * R), o_list = o_pub + al(sizeof(double) * kSoCoopPub * R);
-        size_t o_store = o_list + al(sizeof(int) * M), store = 0;
+        const size_t o_pub = al256(sizeof(SoCoopFlags) * R), o_list = o_pub + al256(sizeof(double) * kSoCoopPub * R);
+        size_t o_store = o_list + al256(sizeof(int) * M), store = 0;
         for (int k = 0; k < R; ++k) {
             const size_t nch = (2 * (moff[k + 1] - moff[k]) + kSoCoopChunk - 1) / kSoCoopChunk;
             store += nch * kSoCoopJd * kSoCoopChunk;
@@ -2015,17 +2056,13 @@ int rsc_optimize_sim3_many(rsc_context* C, const rsc_sim3opt_problem* P, int cou
     }
     RSC_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, C->stream));
     if (helpers > 0) RSC_HIP(hipMemsetAsync(C->d_so_coop.p, 0, sizeof(SoCoopFlags) * R, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_sim3opt(R, reinterpret_cast<const DevSim3OptProb*>(d), helpers, C->h_flag + kFaultWord, C->stream));
-    timing_begin(C, 4);
+    RSC_HIP(timed_launch(C, [&] {
+        return launch_sim3opt(R, reinterpret_cast<const DevSim3OptProb*>(d), helpers, C->h_flag + kFaultWord, C->stream);
+    }));
     RSC_HIP(hipMemcpyAsync(C->h_so_res.p, C->d_so_res.p, res_bytes, hipMemcpyDeviceToHost, C->stream));
     RSC_HIP(hipStreamSynchronize(C->stream));
     if (int e = take_fault(C)) return e;
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+    timing_read(C);
     const double* ho = reinterpret_cast<const double*>(C->h_so_res.p);
     const uint8_t* hk = reinterpret_cast<const uint8_t*>(C->h_so_res.p + r_keep);
     for (int k = 0; k < R; ++k) {
@@ -2064,8 +2101,6 @@ struct rsc_bow {
 };
 
 namespace {
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 void flag_invalid(std::vector<uint32_t>& feat, const uint8_t* valid) {
     for (uint32_t& x : feat) {
         x &= ~kBowInvalid;
@@ -2198,19 +2233,15 @@ int bow_search(rsc_context* C, bool frame_overload, const rsc_bow* const* outer,
         hp[c].nmatches = reinterpret_cast<int32_t*>(d + o_cnt) + c;
     }
     RSC_HIP(hipMemcpyAsync(d, C->h_bow.p, o_cnt, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    int max_nodes = 0;
-    for (int c = 0; c < count; ++c) max_nodes = std::max(max_nodes, outer[c]->n_nodes);
-    RSC_HIP(launch_bow_search(frame_overload, count, max_nodes, reinterpret_cast<const BowPair*>(d + o_pairs), nnratio,
-                              check_ori ? 1 : 0, C->stream));
-    timing_begin(C, 4);
+    RSC_HIP(timed_launch(C, [&] {
+        int max_nodes = 0;
+        for (int c = 0; c < count; ++c) max_nodes = std::max(max_nodes, outer[c]->n_nodes);
+        return launch_bow_search(frame_overload, count, max_nodes, reinterpret_cast<const BowPair*>(d + o_pairs),
+                                 nnratio, check_ori ? 1 : 0, C->stream);
+    }));
     RSC_HIP(hipMemcpyAsync(C->h_bow.p + o_cnt, d + o_cnt, back - o_cnt, hipMemcpyDeviceToHost, C->stream));
     RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+    timing_read(C);
     const int32_t* hc = reinterpret_cast<const int32_t*>(C->h_bow.p + o_cnt);
     for (int c = 0; c < count; ++c) {
         const int on = frame_overload ? inner[c]->n : outer[c]->n;
@@ -2728,67 +2759,58 @@ int rsc_search_by_sim3_many(rsc_context* C, rsc_kfview* const* kf1, rsc_kfview* 
     }
     // layout: pair table | vbAlreadyMatched1/2 flags (host-derived, :972-984) | vnMatch1/2 scratch |
     // outputs (the only part that comes back)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     std::vector<size_t> o_a1(count), o_a2(count), o_m1(count), o_m2(count), o_out(count), o_nf(count);
-    size_t off = al(sizeof(Sim3MatchPair) * count);
+    Arena A;
+    A.take(sizeof(Sim3MatchPair) * count);
     for (int c = 0; c < count; ++c) {
-        o_a1[c] = off; off = al(off + std::max(kf1[c]->n, 1));
-        o_a2[c] = off; off = al(off + std::max(kf2[c]->n, 1));
+        o_a1[c] = A.take((size_t)std::max(kf1[c]->n, 1));
+        o_a2[c] = A.take((size_t)std::max(kf2[c]->n, 1));
     }
-    const size_t up = off;
+    A.end_upload();
     for (int c = 0; c < count; ++c) {
-        o_m1[c] = off; off = al(off + 4 * (size_t)std::max(kf1[c]->n, 1));
-        o_m2[c] = off; off = al(off + 4 * (size_t)std::max(kf2[c]->n, 1));
+        o_m1[c] = A.take(4 * (size_t)std::max(kf1[c]->n, 1));
+        o_m2[c] = A.take(4 * (size_t)std::max(kf2[c]->n, 1));
     }
-    const size_t back = off;
+    A.end_scratch();
     for (int c = 0; c < count; ++c) {
-        o_out[c] = off; off = al(off + 4 * (size_t)std::max(kf1[c]->n, 1));
-        o_nf[c] = off; off += 4;
+        o_out[c] = A.take(4 * (size_t)std::max(kf1[c]->n, 1));
+        o_nf[c] = A.take_packed(4);
     }
-    const size_t bytes = al(off);
-    RSC_HIP(hipSetDevice(C->device));
-    if (int e = C->d_s3m.ensure(bytes)) return e;
-    if (int e = C->h_s3m.ensure(bytes)) return e;
-    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
-    char* h = C->h_s3m.p;
-    char* d = C->d_s3m.p;
-    for (int c = 0; c < count; ++c) {
-        const int n1 = kf1[c]->n, n2 = kf2[c]->n;
-        uint8_t* a1 = reinterpret_cast<uint8_t*>(h + o_a1[c]);
-        uint8_t* a2 = reinterpret_cast<uint8_t*>(h + o_a2[c]);
-        std::memset(a1, 0, (size_t)std::max(n1, 1));
-        std::memset(a2, 0, (size_t)std::max(n2, 1));
-        for (int i = 0; i < n1; ++i) {
-            const int32_t m = matched12[c][i];
-            if (m < -2 || m >= n2) return RSC_ERR_ARG;
-            if (m == -1) continue;
-            a1[i] = 1;
-            if (m >= 0) a2[m] = 1;
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const int n1 = kf1[c]->n, n2 = kf2[c]->n;
+            uint8_t* a1 = reinterpret_cast<uint8_t*>(h + o_a1[c]);
+            uint8_t* a2 = reinterpret_cast<uint8_t*>(h + o_a2[c]);
+            std::memset(a1, 0, (size_t)std::max(n1, 1));
+            std::memset(a2, 0, (size_t)std::max(n2, 1));
+            for (int i = 0; i < n1; ++i) {
+                const int32_t m = matched12[c][i];
+                if (m < -2 || m >= n2) return RSC_ERR_ARG;
+                if (m == -1) continue;
+                a1[i] = 1;
+                if (m >= 0) a2[m] = 1;
+            }
+            Sim3MatchPair p;
+            p.k1 = kf1[c]->hdr;
+            p.k2 = kf2[c]->hdr;
+            std::memcpy(p.R12, R12 + 9 * c, sizeof(p.R12));
+            std::memcpy(p.t12, t12 + 3 * c, sizeof(p.t12));
+            p.already1 = reinterpret_cast<const uint8_t*>(d + o_a1[c]);
+            p.already2 = reinterpret_cast<const uint8_t*>(d + o_a2[c]);
+            p.m1 = reinterpret_cast<int32_t*>(d + o_m1[c]);
+            p.m2 = reinterpret_cast<int32_t*>(d + o_m2[c]);
+            p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+            p.nfound = reinterpret_cast<int32_t*>(d + o_nf[c]);
+            std::memcpy(h + sizeof(Sim3MatchPair) * c, &p, sizeof(p));
         }
-        Sim3MatchPair p;
-        p.k1 = kf1[c]->hdr;
-        p.k2 = kf2[c]->hdr;
-        std::memcpy(p.R12, R12 + 9 * c, sizeof(p.R12));
-        std::memcpy(p.t12, t12 + 3 * c, sizeof(p.t12));
-        p.already1 = reinterpret_cast<const uint8_t*>(d + o_a1[c]);
-        p.already2 = reinterpret_cast<const uint8_t*>(d + o_a2[c]);
-        p.m1 = reinterpret_cast<int32_t*>(d + o_m1[c]);
-        p.m2 = reinterpret_cast<int32_t*>(d + o_m2[c]);
-        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
-        p.nfound = reinterpret_cast<int32_t*>(d + o_nf[c]);
-        std::memcpy(h + sizeof(Sim3MatchPair) * c, &p, sizeof(p));
-    }
-    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_search_by_sim3(count, max_points, reinterpret_cast<const Sim3MatchPair*>(d), th, C->stream));
-    timing_begin(C, 4);
-    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_search_by_sim3(count, max_points, reinterpret_cast<const Sim3MatchPair*>(d), th, C->stream);
+    };
+    if (int e = arena_run(C, C->d_s3m, C->h_s3m, A, fill, launch)) return e;
+    const char* h = C->h_s3m.p;
     for (int c = 0; c < count; ++c) {
         if (kf1[c]->n) std::memcpy(out12[c], h + o_out[c], 4 * (size_t)kf1[c]->n);
         if (nfound) std::memcpy(&nfound[c], h + o_nf[c], 4);
@@ -2942,69 +2964,61 @@ int rsc_search_by_projection_many(rsc_context* C, rsc_frameview* const* frames, 
     }
     // layout: problem table | already flags | frame_mp  (uploaded)  | windows | candidates | claims  (scratch)  |
     // out | nmatches, rounds  (the part that comes back)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     std::vector<size_t> o_al(count), o_mp(count), o_rec(count), o_cd(count), o_cl(count), o_out(count), o_cnt(count);
     int max_kf_points = 0;
-    size_t off = al(sizeof(FrameProjProblem) * count);
+    Arena A;
+    A.take(sizeof(FrameProjProblem) * count);
     for (int c = 0; c < count; ++c) {
-        o_al[c] = off; off = al(off + (size_t)std::max(kfs[c]->n, 1));
-        o_mp[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
+        o_al[c] = A.take((size_t)std::max(kfs[c]->n, 1));
+        o_mp[c] = A.take(4 * (size_t)std::max(frames[c]->n, 1));
     }
-    const size_t up = off;
+    A.end_upload();
     for (int c = 0; c < count; ++c) {
-        o_rec[c] = off; off = al(off + sizeof(ProjRec) * (size_t)std::max(kfs[c]->n, 1));
-        o_cd[c] = off; off = al(off + sizeof(ProjCand) * (size_t)std::max(kfs[c]->n, 1));
+        const size_t nk = (size_t)std::max(kfs[c]->n, 1);
+        o_rec[c] = A.take(sizeof(ProjRec) * nk);
+        o_cd[c] = A.take(sizeof(ProjCand) * nk);
+        o_cl[c] = A.take(4 * nk);
         max_kf_points = std::max(max_kf_points, kfs[c]->n);
-        o_cl[c] = off; off = al(off + 4 * (size_t)std::max(kfs[c]->n, 1));
     }
-    const size_t back = off;
+    A.end_scratch();
     for (int c = 0; c < count; ++c) {
-        o_out[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
-        o_cnt[c] = off; off += 8;
+        o_out[c] = A.take(4 * (size_t)std::max(frames[c]->n, 1));
+        o_cnt[c] = A.take_packed(8);
     }
-    const size_t bytes = al(off);
-    RSC_HIP(hipSetDevice(C->device));
-    if (int e = C->d_fp.ensure(bytes)) return e;
-    if (int e = C->h_fp.ensure(bytes)) return e;
-    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
-    char* h = C->h_fp.p;
-    char* d = C->d_fp.p;
-    for (int c = 0; c < count; ++c) {
-        const rsc_kfview& k = *kfs[c];
-        if (k.n) std::memcpy(h + o_al[c], already[c], (size_t)k.n);
-        if (frames[c]->n) std::memcpy(h + o_mp[c], frame_mp[c], 4 * (size_t)frames[c]->n);
-        FrameProjProblem p;
-        p.F = frames[c]->hdr;
-        p.K.mp_state = k.dev.mp_state;
-        p.K.mp_pos = k.dev.mp_pos;
-        p.K.mp_dmax = k.dev.mp_dmax;
-        p.K.mp_dmin = k.dev.mp_dmin;
-        p.K.mp_desc = reinterpret_cast<const ProjDesc*>(k.dev.mp_desc);
-        p.K.angle = k.has_angles ? k.d_angle.p : nullptr;
-        p.K.n = k.n;
-        std::memcpy(p.Tcw, Tcw + 16 * (size_t)c, sizeof(p.Tcw));
-        p.already = reinterpret_cast<const uint8_t*>(d + o_al[c]);
-        p.frame_mp = reinterpret_cast<const int32_t*>(d + o_mp[c]);
-        p.rec = reinterpret_cast<ProjRec*>(d + o_rec[c]);
-        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
-        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
-        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
-        p.nmatches = reinterpret_cast<int32_t*>(d + o_cnt[c]);
-        p.rounds = p.nmatches + 1;
-        std::memcpy(h + sizeof(FrameProjProblem) * c, &p, sizeof(p));
-    }
-    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_search_by_projection(count, max_kf_points, reinterpret_cast<const FrameProjProblem*>(d), th,
-                                        orb_dist, check_orientation ? 1 : 0, C->stream));
-    timing_begin(C, 4);
-    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const rsc_kfview& k = *kfs[c];
+            if (k.n) std::memcpy(h + o_al[c], already[c], (size_t)k.n);
+            if (frames[c]->n) std::memcpy(h + o_mp[c], frame_mp[c], 4 * (size_t)frames[c]->n);
+            FrameProjProblem p;
+            p.F = frames[c]->hdr;
+            p.K.mp_state = k.dev.mp_state;
+            p.K.mp_pos = k.dev.mp_pos;
+            p.K.mp_dmax = k.dev.mp_dmax;
+            p.K.mp_dmin = k.dev.mp_dmin;
+            p.K.mp_desc = reinterpret_cast<const ProjDesc*>(k.dev.mp_desc);
+            p.K.angle = k.has_angles ? k.d_angle.p : nullptr;
+            p.K.n = k.n;
+            std::memcpy(p.Tcw, Tcw + 16 * (size_t)c, sizeof(p.Tcw));
+            p.already = reinterpret_cast<const uint8_t*>(d + o_al[c]);
+            p.frame_mp = reinterpret_cast<const int32_t*>(d + o_mp[c]);
+            p.rec = reinterpret_cast<ProjRec*>(d + o_rec[c]);
+            p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+            p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+            p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+            p.nmatches = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+            p.rounds = p.nmatches + 1;
+            std::memcpy(h + sizeof(FrameProjProblem) * c, &p, sizeof(p));
+        }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_search_by_projection(count, max_kf_points, reinterpret_cast<const FrameProjProblem*>(d), th,
+                                           orb_dist, check_orientation ? 1 : 0, C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch)) return e;
+    const char* h = C->h_fp.p;
     for (int c = 0; c < count; ++c) {
         if (frames[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)frames[c]->n);
         if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
@@ -3403,18 +3417,12 @@ int kfdb_query(rsc_kfdb* db, uint64_t qid, int n, const uint32_t* id, const doub
     q.n = n;
     q.loop = loop;
     q.min_score = min_score;
-    timing_begin(C, 3);
     DevKFDB d = db->dev();
     d.qvals = reinterpret_cast<const double*>(db->qbuf.p + vo);
-    RSC_HIP(launch_kfdb_query(d, q, C->stream));
-    timing_begin(C, 4);
+    RSC_HIP(timed_launch(C, [&] { return launch_kfdb_query(d, q, C->stream); }));
     RSC_HIP(launch_copy_bytes(db->out.p, h, 4 * (H + 1), C->stream));  // written into pinned memory
     RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+    timing_read(C);
     const int32_t* o = reinterpret_cast<const int32_t*>(h);
     *n_cand = o[0];
     std::memcpy(cand, o + 1, 4 * (size_t)o[0]);
@@ -4498,65 +4506,56 @@ int rsc_search_by_projection_kf_many(rsc_context* C, rsc_kfview* const* kfs, rsc
     }
     // layout: problem table | already flags | occupied flags  (uploaded)  | windows | candidates | claims
     // (scratch)  | out | nmatches, rounds  (the part that comes back)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     std::vector<size_t> o_al(count), o_oc(count), o_rec(count), o_cd(count), o_cl(count), o_out(count), o_cnt(count);
     int max_points = 0;
-    size_t off = al(sizeof(KfProjProblem) * count);
+    Arena A;
+    A.take(sizeof(KfProjProblem) * count);
     for (int c = 0; c < count; ++c) {
-        o_al[c] = off; off = al(off + (size_t)std::max(points[c]->n, 1));
-        o_oc[c] = off; off = al(off + (size_t)std::max(kfs[c]->n, 1));
+        o_al[c] = A.take((size_t)std::max(points[c]->n, 1));
+        o_oc[c] = A.take((size_t)std::max(kfs[c]->n, 1));
     }
-    const size_t up = off;
+    A.end_upload();
     for (int c = 0; c < count; ++c) {
         const size_t np = (size_t)std::max(points[c]->n, 1);
-        o_rec[c] = off; off = al(off + sizeof(ProjRec) * np);
-        o_cd[c] = off; off = al(off + sizeof(ProjCand) * np);
-        o_cl[c] = off; off = al(off + 4 * np);
+        o_rec[c] = A.take(sizeof(ProjRec) * np);
+        o_cd[c] = A.take(sizeof(ProjCand) * np);
+        o_cl[c] = A.take(4 * np);
         max_points = std::max(max_points, points[c]->n);
     }
-    const size_t back = off;
+    A.end_scratch();
     for (int c = 0; c < count; ++c) {
-        o_out[c] = off; off = al(off + 4 * (size_t)std::max(kfs[c]->n, 1));
-        o_cnt[c] = off; off += 8;
+        o_out[c] = A.take(4 * (size_t)std::max(kfs[c]->n, 1));
+        o_cnt[c] = A.take_packed(8);
     }
-    const size_t bytes = al(off);
-    RSC_HIP(hipSetDevice(C->device));
-    if (int e = C->d_fp.ensure(bytes)) return e;
-    if (int e = C->h_fp.ensure(bytes)) return e;
-    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
-    char* h = C->h_fp.p;
-    char* d = C->d_fp.p;
-    for (int c = 0; c < count; ++c) {
-        const rsc_kfview& k = *kfs[c];
-        const rsc_mpview& m = *points[c];
-        if (m.n) std::memcpy(h + o_al[c], already[c], (size_t)m.n);
-        if (k.n) std::memcpy(h + o_oc[c], occupied[c], (size_t)k.n);
-        KfProjProblem p;
-        p.K = kfp_kf_of(k);
-        p.P = m.dev;
-        std::memcpy(p.Scw, Scw + 16 * (size_t)c, sizeof(p.Scw));
-        p.already = reinterpret_cast<const uint8_t*>(d + o_al[c]);
-        p.occupied = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
-        p.rec = reinterpret_cast<ProjRec*>(d + o_rec[c]);
-        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
-        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
-        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
-        p.nmatches = reinterpret_cast<int32_t*>(d + o_cnt[c]);
-        p.rounds = p.nmatches + 1;
-        std::memcpy(h + sizeof(KfProjProblem) * c, &p, sizeof(p));
-    }
-    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_search_by_projection_kf(count, max_points, reinterpret_cast<const KfProjProblem*>(d), (float)th,
-                                           C->stream));
-    timing_begin(C, 4);
-    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const rsc_kfview& k = *kfs[c];
+            const rsc_mpview& m = *points[c];
+            if (m.n) std::memcpy(h + o_al[c], already[c], (size_t)m.n);
+            if (k.n) std::memcpy(h + o_oc[c], occupied[c], (size_t)k.n);
+            KfProjProblem p;
+            p.K = kfp_kf_of(k);
+            p.P = m.dev;
+            std::memcpy(p.Scw, Scw + 16 * (size_t)c, sizeof(p.Scw));
+            p.already = reinterpret_cast<const uint8_t*>(d + o_al[c]);
+            p.occupied = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
+            p.rec = reinterpret_cast<ProjRec*>(d + o_rec[c]);
+            p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+            p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+            p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+            p.nmatches = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+            p.rounds = p.nmatches + 1;
+            std::memcpy(h + sizeof(KfProjProblem) * c, &p, sizeof(p));
+        }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_search_by_projection_kf(count, max_points, reinterpret_cast<const KfProjProblem*>(d),
+                                              (float)th, C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch)) return e;
+    const char* h = C->h_fp.p;
     for (int c = 0; c < count; ++c) {
         if (kfs[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)kfs[c]->n);
         if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
@@ -4576,39 +4575,34 @@ int rsc_fuse_sim3_many(rsc_context* C, rsc_kfview* const* kfs, int count, rsc_mp
         if (np && (!in_kf[c] || !best_idx[c])) return RSC_ERR_ARG;
     }
     // layout: problem table | in_kf flags  (uploaded)  | best_idx  (comes back)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t row = al((size_t)std::max(np, 1)), row4 = al(4 * (size_t)std::max(np, 1));
-    const size_t o_in = al(sizeof(KfFuseProblem) * count);
-    const size_t back = o_in + row * (size_t)count;
-    const size_t bytes = back + row4 * (size_t)count;
-    RSC_HIP(hipSetDevice(C->device));
-    if (int e = C->d_fp.ensure(bytes)) return e;
-    if (int e = C->h_fp.ensure(bytes)) return e;
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    char* h = C->h_fp.p;
-    char* d = C->d_fp.p;
+    // (rows of one stride each: every problem has the same np; no scratch)
+    const size_t row = al256((size_t)std::max(np, 1)), row4 = al256(4 * (size_t)std::max(np, 1));
+    Arena A;
+    A.take(sizeof(KfFuseProblem) * count);
+    const size_t o_in = A.take(row * (size_t)count);
+    A.end_upload();
+    A.end_scratch();
+    const size_t o_best = A.take(row4 * (size_t)count);
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            if (np) std::memcpy(h + o_in + row * c, in_kf[c], (size_t)np);
+            KfFuseProblem p;
+            p.K = kfp_kf_of(*kfs[c]);
+            std::memcpy(p.Scw, Scw + 16 * (size_t)c, sizeof(p.Scw));
+            p.in_kf = reinterpret_cast<const uint8_t*>(d + o_in + row * c);
+            p.best_idx = reinterpret_cast<int32_t*>(d + o_best + row4 * c);
+            std::memcpy(h + sizeof(KfFuseProblem) * c, &p, sizeof(p));
+        }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_fuse_sim3(count, &points->dev, np, reinterpret_cast<const KfFuseProblem*>(d), th, C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch, /*download=*/np != 0)) return e;
+    const char* h = C->h_fp.p;
     for (int c = 0; c < count; ++c) {
-        if (np) std::memcpy(h + o_in + row * c, in_kf[c], (size_t)np);
-        KfFuseProblem p;
-        p.K = kfp_kf_of(*kfs[c]);
-        std::memcpy(p.Scw, Scw + 16 * (size_t)c, sizeof(p.Scw));
-        p.in_kf = reinterpret_cast<const uint8_t*>(d + o_in + row * c);
-        p.best_idx = reinterpret_cast<int32_t*>(d + back + row4 * c);
-        std::memcpy(h + sizeof(KfFuseProblem) * c, &p, sizeof(p));
-    }
-    RSC_HIP(hipMemcpyAsync(d, h, back, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_fuse_sim3(count, &points->dev, np, reinterpret_cast<const KfFuseProblem*>(d), th, C->stream));
-    timing_begin(C, 4);
-    if (np) RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        C->last_ms[2] = ms;
-    }
-    for (int c = 0; c < count; ++c) {
-        const int32_t* b = reinterpret_cast<const int32_t*>(h + back + row4 * c);
+        const int32_t* b = reinterpret_cast<const int32_t*>(h + o_best + row4 * c);
         int nf = 0;
         for (int i = 0; i < np; ++i) {
             best_idx[c][i] = b[i];
@@ -4704,83 +4698,71 @@ int local_points_impl(rsc_context* C, rsc_frameview* const* frames, rsc_mpview* 
     }
     // layout: problem table | skip | has_obs | frame_occ | track (matcher-only)  (uploaded)  | windows |
     // candidates | claims  (scratch)  | track (fused) | out | nmatches, nToMatch, rounds  (what comes back)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     std::vector<size_t> o_sk(count), o_ho(count), o_oc(count), o_tr(count), o_rec(count), o_cd(count), o_cl(count),
         o_out(count), o_cnt(count);
     int max_points = 0;
-    size_t off = al(sizeof(LocalProjProblem) * count);
+    Arena A;
+    A.take(sizeof(LocalProjProblem) * count);
     for (int c = 0; c < count; ++c) {
         const size_t np = (size_t)std::max(points[c]->n, 1), nf = (size_t)std::max(frames[c]->n, 1);
-        o_sk[c] = off; off = al(off + np);
-        o_ho[c] = off; off = al(off + np);
-        o_oc[c] = off; off = al(off + nf);
-        if (!fused) { o_tr[c] = off; off = al(off + sizeof(LpTrack) * np); }
+        o_sk[c] = A.take(np);
+        o_ho[c] = A.take(np);
+        o_oc[c] = A.take(nf);
+        if (!fused) o_tr[c] = A.take(sizeof(LpTrack) * np);
     }
-    const size_t up = off;
+    A.end_upload();
     for (int c = 0; c < count; ++c) {
         const size_t np = (size_t)std::max(points[c]->n, 1);
-        o_rec[c] = off; off = al(off + sizeof(LpRec) * np);
-        o_cd[c] = off; off = al(off + sizeof(ProjCand) * np);
-        o_cl[c] = off; off = al(off + 4 * np);
+        o_rec[c] = A.take(sizeof(LpRec) * np);
+        o_cd[c] = A.take(sizeof(ProjCand) * np);
+        o_cl[c] = A.take(4 * np);
         max_points = std::max(max_points, points[c]->n);
     }
-    const size_t back = off;
+    A.end_scratch();
     for (int c = 0; c < count; ++c) {
         const size_t np = (size_t)std::max(points[c]->n, 1);
-        if (fused) { o_tr[c] = off; off = al(off + sizeof(LpTrack) * np); }
-        o_out[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
-        o_cnt[c] = off; off += 16;
+        if (fused) o_tr[c] = A.take(sizeof(LpTrack) * np);
+        o_out[c] = A.take(4 * (size_t)std::max(frames[c]->n, 1));
+        o_cnt[c] = A.take_packed(16);
     }
-    const size_t bytes = al(off);
-    RSC_HIP(hipSetDevice(C->device));
-    if (int e = C->d_fp.ensure(bytes)) return e;
-    if (int e = C->h_fp.ensure(bytes)) return e;
-    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
-    char* h = C->h_fp.p;
-    char* d = C->d_fp.p;
-    for (int c = 0; c < count; ++c) {
-        const rsc_frameview& f = *frames[c];
-        const rsc_mpview& m = *points[c];
-        if (m.n) {
-            std::memcpy(h + o_sk[c], skip[c], (size_t)m.n);
-            std::memcpy(h + o_ho[c], has_obs[c], (size_t)m.n);
-            if (!fused) std::memcpy(h + o_tr[c], track[c], sizeof(LpTrack) * (size_t)m.n);
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const rsc_frameview& f = *frames[c];
+            const rsc_mpview& m = *points[c];
+            if (m.n) {
+                std::memcpy(h + o_sk[c], skip[c], (size_t)m.n);
+                std::memcpy(h + o_ho[c], has_obs[c], (size_t)m.n);
+                if (!fused) std::memcpy(h + o_tr[c], track[c], sizeof(LpTrack) * (size_t)m.n);
+            }
+            if (f.n) std::memcpy(h + o_oc[c], frame_occ[c], (size_t)f.n);
+            LocalProjProblem p;
+            p.F = f.hdr;
+            p.u_right = f.d_uright.p;
+            p.mbf = f.mbf;
+            p.P = m.dev;
+            if (fused) std::memcpy(p.Tcw, Tcw + 16 * (size_t)c, sizeof(p.Tcw));
+            else std::memset(p.Tcw, 0, sizeof(p.Tcw));
+            p.skip = reinterpret_cast<const uint8_t*>(d + o_sk[c]);
+            p.has_obs = reinterpret_cast<const uint8_t*>(d + o_ho[c]);
+            p.frame_occ = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
+            p.track = reinterpret_cast<LpTrack*>(d + o_tr[c]);
+            p.rec = reinterpret_cast<LpRec*>(d + o_rec[c]);
+            p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+            p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+            p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+            p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+            std::memcpy(h + sizeof(LocalProjProblem) * c, &p, sizeof(p));
         }
-        if (f.n) std::memcpy(h + o_oc[c], frame_occ[c], (size_t)f.n);
-        LocalProjProblem p;
-        p.F = f.hdr;
-        p.u_right = f.d_uright.p;
-        p.mbf = f.mbf;
-        p.P = m.dev;
-        if (fused) std::memcpy(p.Tcw, Tcw + 16 * (size_t)c, sizeof(p.Tcw));
-        else std::memset(p.Tcw, 0, sizeof(p.Tcw));
-        p.skip = reinterpret_cast<const uint8_t*>(d + o_sk[c]);
-        p.has_obs = reinterpret_cast<const uint8_t*>(d + o_ho[c]);
-        p.frame_occ = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
-        p.track = reinterpret_cast<LpTrack*>(d + o_tr[c]);
-        p.rec = reinterpret_cast<LpRec*>(d + o_rec[c]);
-        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
-        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
-        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
-        p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
-        std::memcpy(h + sizeof(LocalProjProblem) * c, &p, sizeof(p));
-    }
-    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_search_local_points(count, max_points, reinterpret_cast<const LocalProjProblem*>(d), fused ? 1 : 0,
-                                       cos_limit, th, nn_ratio, C->timing ? C->ev[5] : nullptr, C->stream));
-    timing_begin(C, 4);
-    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {  // rsc_context_last_kernel_timing: [0] setup kernel, [1] rounds kernel, [2] both
-        float ms = 0, a = 0, b = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        (void)hipEventElapsedTime(&a, C->ev[3], C->ev[5]);
-        (void)hipEventElapsedTime(&b, C->ev[5], C->ev[4]);
-        C->last_ms[0] = a;
-        C->last_ms[1] = b;
-        C->last_ms[2] = ms;
-    }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_search_local_points(count, max_points, reinterpret_cast<const LocalProjProblem*>(d),
+                                          fused ? 1 : 0, cos_limit, th, nn_ratio,
+                                          C->timing ? C->ev[5] : nullptr, C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch, true, /*mid=*/true)) return e;
+    const char* h = C->h_fp.p;
     for (int c = 0; c < count; ++c) {
         if (frames[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)frames[c]->n);
         if (fused && points[c]->n) std::memcpy(track[c], h + o_tr[c], sizeof(LpTrack) * (size_t)points[c]->n);
@@ -4915,72 +4897,58 @@ int rsc_search_by_projection_last_many(rsc_context* C, rsc_frameview* const* fra
         if (frames[c]->n && !out[c]) return RSC_ERR_ARG;
     // layout: problem table | frame_occ  (uploaded)  | windows | candidates | claims  (scratch)  |
     // out | nmatches, mode, rounds, claims  (what comes back)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     std::vector<size_t> o_oc(count), o_rec(count), o_cd(count), o_cl(count), o_out(count), o_cnt(count);
     int max_slots = 0;
-    size_t off = al(sizeof(LastProjProblem) * count);
-    for (int c = 0; c < count; ++c) {
-        o_oc[c] = off; off = al(off + (size_t)std::max(frames[c]->n, 1));
-    }
-    const size_t up = off;
+    Arena A;
+    A.take(sizeof(LastProjProblem) * count);
+    for (int c = 0; c < count; ++c) o_oc[c] = A.take((size_t)std::max(frames[c]->n, 1));
+    A.end_upload();
     for (int c = 0; c < count; ++c) {
         const size_t nl = (size_t)std::max(lasts[c]->n, 1);
-        o_rec[c] = off; off = al(off + sizeof(LpRec) * nl);
-        o_cd[c] = off; off = al(off + sizeof(ProjCand) * nl);
-        o_cl[c] = off; off = al(off + 4 * nl);
+        o_rec[c] = A.take(sizeof(LpRec) * nl);
+        o_cd[c] = A.take(sizeof(ProjCand) * nl);
+        o_cl[c] = A.take(4 * nl);
         max_slots = std::max(max_slots, lasts[c]->n);
     }
-    const size_t back = off;
+    A.end_scratch();
     for (int c = 0; c < count; ++c) {
-        o_out[c] = off; off = al(off + 4 * (size_t)std::max(frames[c]->n, 1));
-        o_cnt[c] = off; off += 16;
+        o_out[c] = A.take(4 * (size_t)std::max(frames[c]->n, 1));
+        o_cnt[c] = A.take_packed(16);
     }
-    const size_t bytes = al(off);
-    RSC_HIP(hipSetDevice(C->device));
-    if (int e = C->d_fp.ensure(bytes)) return e;
-    if (int e = C->h_fp.ensure(bytes)) return e;
-    RSC_HIP(hipStreamSynchronize(C->stream));  // the pinned mirror is free again
-    char* h = C->h_fp.p;
-    char* d = C->d_fp.p;
-    for (int c = 0; c < count; ++c) {
-        const rsc_frameview& f = *frames[c];
-        const rsc_lastframe& l = *lasts[c];
-        if (frame_occ && frame_occ[c]) {
-            if (f.n) std::memcpy(h + o_oc[c], frame_occ[c], (size_t)f.n);
-        } else {
-            std::memset(h + o_oc[c], 0, (size_t)std::max(f.n, 1));
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const rsc_frameview& f = *frames[c];
+            const rsc_lastframe& l = *lasts[c];
+            if (frame_occ && frame_occ[c]) {
+                if (f.n) std::memcpy(h + o_oc[c], frame_occ[c], (size_t)f.n);
+            } else {
+                std::memset(h + o_oc[c], 0, (size_t)std::max(f.n, 1));
+            }
+            LastProjProblem p;
+            p.F = f.hdr;
+            p.u_right = f.d_uright.p;
+            p.mbf = f.mbf;
+            p.mode = last_mode(Tcw_cur + 16 * (size_t)c, Tcw_last + 16 * (size_t)c, mb[c]);
+            p.L = l.dev;
+            std::memcpy(p.Tcw, Tcw_cur + 16 * (size_t)c, sizeof(p.Tcw));
+            p.frame_occ = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
+            p.rec = reinterpret_cast<LpRec*>(d + o_rec[c]);
+            p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
+            p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
+            p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
+            p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+            std::memcpy(h + sizeof(LastProjProblem) * c, &p, sizeof(p));
         }
-        LastProjProblem p;
-        p.F = f.hdr;
-        p.u_right = f.d_uright.p;
-        p.mbf = f.mbf;
-        p.mode = last_mode(Tcw_cur + 16 * (size_t)c, Tcw_last + 16 * (size_t)c, mb[c]);
-        p.L = l.dev;
-        std::memcpy(p.Tcw, Tcw_cur + 16 * (size_t)c, sizeof(p.Tcw));
-        p.frame_occ = reinterpret_cast<const uint8_t*>(d + o_oc[c]);
-        p.rec = reinterpret_cast<LpRec*>(d + o_rec[c]);
-        p.cand = reinterpret_cast<ProjCand*>(d + o_cd[c]);
-        p.claim = reinterpret_cast<int32_t*>(d + o_cl[c]);
-        p.out = reinterpret_cast<int32_t*>(d + o_out[c]);
-        p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
-        std::memcpy(h + sizeof(LastProjProblem) * c, &p, sizeof(p));
-    }
-    RSC_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, C->stream));
-    timing_begin(C, 3);
-    RSC_HIP(launch_search_by_projection_last(count, max_slots, reinterpret_cast<const LastProjProblem*>(d), th,
-                                             check_orientation ? 1 : 0, C->timing ? C->ev[5] : nullptr, C->stream));
-    timing_begin(C, 4);
-    RSC_HIP(hipMemcpyAsync(h + back, d + back, bytes - back, hipMemcpyDeviceToHost, C->stream));
-    RSC_HIP(hipStreamSynchronize(C->stream));
-    if (C->timing) {  // rsc_context_last_kernel_timing: [0] setup kernel, [1] rounds kernel, [2] both
-        float ms = 0, a = 0, b = 0;
-        (void)hipEventElapsedTime(&ms, C->ev[3], C->ev[4]);
-        (void)hipEventElapsedTime(&a, C->ev[3], C->ev[5]);
-        (void)hipEventElapsedTime(&b, C->ev[5], C->ev[4]);
-        C->last_ms[0] = a;
-        C->last_ms[1] = b;
-        C->last_ms[2] = ms;
-    }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_search_by_projection_last(count, max_slots, reinterpret_cast<const LastProjProblem*>(d), th,
+                                                check_orientation ? 1 : 0, C->timing ? C->ev[5] : nullptr,
+                                                C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch, true, /*mid=*/true)) return e;
+    const char* h = C->h_fp.p;
     for (int c = 0; c < count; ++c) {
         if (frames[c]->n) std::memcpy(out[c], h + o_out[c], 4 * (size_t)frames[c]->n);
         if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
