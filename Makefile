@@ -11,16 +11,16 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
-     facade_lastproj_test arena_test
+     facade_lastproj_test arena_test rounds_test
 
-OBJS = $(addprefix $(LIBDIR)/,kernels.o mlpnp.o poseopt.o sim3opt.o orbmatch.o sim3match.o frameproj.o kfproj.o \
-         localproj.o lastproj.o kfdb.o bowvoc.o rsc_api.o)
+include $(CSRC)/objs.mk
+OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
 
 $(LIBDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/rsc_api.o: $(CSRC)/rsc_api.cpp $(HDRS)
+$(LIBDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -70,6 +70,20 @@ $(LIBDIR)/arena_test_san: tests/cpp/arena_test.cpp $(CSRC)/rsc_arena.h
 	mkdir -p $(LIBDIR)
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
 
+# TEST-ONLY host programs: the drivers' bookkeeping (rsc_rounds.h) against the former driver loops
+# (tests/test_cpu_rounds.py); the second build runs under the host sanitizers
+rounds_test: $(LIBDIR)/rounds_test $(LIBDIR)/rounds_test_san
+
+ROUNDS_DEPS = tests/cpp/rounds_test.cpp $(CSRC)/rsc_rounds.h $(CSRC)/rsc_engine.h include/rsc.h
+
+$(LIBDIR)/rounds_test: $(ROUNDS_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/rounds_test_san: $(ROUNDS_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -96,4 +110,4 @@ clean:
 	       tests/localproj_emu/build tests/lastproj_emu/build
 
 .PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu facade_localproj_test facade_lastproj_test facade_test facade_proj_test facade_loopproj_test \
-        facade_voc_test chase_mirror_test arena_test clean
+        facade_voc_test chase_mirror_test arena_test rounds_test clean

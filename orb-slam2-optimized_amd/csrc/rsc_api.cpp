@@ -6,93 +6,28 @@
 //   Sim3: x1 float4[N] = (X1c, maxErr1), x2 float4[N] = (X2c, maxErr2), pim float4[N].
 // Per context (reused across calls, grown on demand): the rand() jump table (2.1 MB), pose
 // records float[H][12|24], counts int32[H], inlier bitsets uint64[H][W], launch descriptors.
-#include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
-#include <algorithm>
 #include <array>
-#include <chrono>
 #include <cmath>
 #include <cstring>
-#include <string>
-#include <vector>
 #include <memory>
-#include "../../include/rsc.h"
+#include "rsc_host.h"
+#include "rsc_rounds.h"
 #include "rsc_arena.h"
-#include "rsc_kernels.h"
-#include "rsc_engine.h"
 #include "rsc_poseopt.h"
 #include "rsc_sim3opt.h"
 #include "rsc_orbmatch.h"
-#include "rsc_sim3match.h"
-#include "rsc_frameproj.h"
 #include "rsc_kfproj.h"
 #include "rsc_localproj.h"
-#include "rsc_lastproj.h"
-#include "rsc_sim3compose.h"
 #include "rsc_kfdb.h"
 #include "rsc_bowvoc.h"
 
 using namespace rsc;
 
-namespace {
-
 thread_local std::string g_last_error;
 
-#define RSC_HIP(call)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (call);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            g_last_error = std::string(#call) + ": " + hipGetErrorString(_e);                  \
-            return RSC_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max(n, (size_t)64);
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e != hipSuccess) {
-            g_last_error = std::string("hipMalloc: ") + hipGetErrorString(e);
-            return RSC_ERR_OOM;
-        }
-        cap = want;
-        return 0;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-template <typename T>
-struct PinBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max(n, (size_t)64);
-        hipError_t e = hipHostMalloc(&p, want * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            g_last_error = std::string("hipHostMalloc: ") + hipGetErrorString(e);
-            return RSC_ERR_OOM;
-        }
-        cap = want;
-        return 0;
-    }
-    ~PinBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-};
+namespace {
 
 // XCD-aware order of a workgroup table.  The dispatcher deals blocks round-robin over the 8 XCDs
 // (blocks b and b + 8 share one L2; MI355X_MICROARCH.md "Workgroup dispatch, XCD placement"), and
@@ -210,149 +145,6 @@ int ppt_for(int n) {
 
 constexpr int kSoCoopCUs = 256;  // OptimizeSim3's cooperative form: workgroups per launch at most (MI355X CUs)
 constexpr int kFaultWord = 4;  // rsc_context::h_flag[4]: the split eigen stage's fault word
-
-struct rsc_context {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    RngTable table;
-    DevBuf<uint32_t> d_table;
-    // speculation work buffers
-    DevBuf<float> d_poses;
-    DevBuf<int32_t> d_counts;
-    DevBuf<uint64_t> d_masks;
-    DevBuf<int32_t> d_samples;
-    DevBuf<double> d_stage;  // quad path: per-hypothesis stage records between the two solve kernels
-    DevBuf<double> d_berr;   // pnp_betas_kernel results for the scan: error per (approximation, record)
-    DevBuf<float> d_bpose;   //   float pose [12] per (approximation, record)
-    DevBuf<float> d_gather;  // gathered pose records (+ their indices)
-    DevBuf<double> d_mposes; // MLPnP hypothesis poses, double[12] per record
-    DevBuf<char> d_desc;
-    PinBuf<char> h_desc;
-    PinBuf<int32_t> h_counts;
-    PinBuf<int32_t> h_qual;  // PnP rounds: 1 when a problem has a hypothesis reaching min_inliers
-    // PnP work tables (eigen / betas / scan workgroups) on the device, uploaded when the round's shape
-    // (pnp_tab_key) changes instead of with every round's descriptors
-    DevBuf<char> d_pnp_tab;
-    std::vector<int> pnp_tab_key;
-    size_t pnp_tab_quad[3] = {0, 0, 0}, pnp_tab_solve[3] = {0, 0, 0}, pnp_tab_scan = 0;
-    // resident pnp_scan_kernel<PPT> workgroups of the device, [log2 PPT] (occupancy query x CU count,
-    // read at the first round that needs it; 0: not read yet)
-    int pnp_scan_capacity[6] = {0, 0, 0, 0, 0, 0};
-    PinBuf<float> h_small;
-    PinBuf<float> h_pick;  // Sim3 pick records of the last round, [solver][16]
-    DevBuf<char> d_refine;
-    DevBuf<RefineSelOut> d_selout;  // pnp_select_refine_kernel results of the last fused round
-    PinBuf<RefineSelOut> h_selout;
-    // PoseOptimization: packed inputs (problems | xw | uv), edge error scratch, results (outliers | poses)
-    DevBuf<char> d_po_in;
-    // OptimizeSim3: packed inputs (problems | e12 | e21 | uv), edge errors, results (out | keep)
-    DevBuf<char> d_so_in;
-    PinBuf<char> h_so_in;
-    DevBuf<char> d_so_res;
-    PinBuf<char> h_so_res;
-    DevBuf<char> d_po_res;
-    PinBuf<char> h_po_in;
-    PinBuf<char> h_po_res;
-    // SearchBySim3: packed KeyFrames + pair table + scratch + outputs (device, pinned mirror)
-    DevBuf<char> d_s3m;
-    PinBuf<char> h_s3m;
-    // where the last rsc_search_by_sim3_many left each pair's vnMatch1 / vnMatch2 in d_s3m
-    // (rsc_diag_sim3match_directions); empty before the first call and after a failed one
-    struct S3mPair { size_t o_m1, o_m2; int n1, n2; };
-    std::vector<S3mPair> s3m_last;
-    // SearchByBoW: pair table + output vectors + match counts (device, pinned mirror)
-    DevBuf<char> d_bow;
-    PinBuf<char> h_bow;
-    // SearchByProjection (Frame, KeyFrame): problem table + flags + per-MapPoint scratch + outputs
-    DevBuf<char> d_fp;
-    PinBuf<char> h_fp;
-    int mask_words = 0;  // per hypothesis, last speculation
-    bool keep_samples = true;
-    // timing
-    bool timing = false;
-    hipEvent_t ev[12] = {};  // [0..5] phase marks, [6+2g], [7+2g] eigen-stage kernel of sample-size group g
-    double last_ms[6] = {0, 0, 0, 0, 0, 0};
-    // host-side phase clock of the last PnP iterate_many (diagnostic): microseconds from entry to
-    // [0] speculation inputs built, [1] kernels enqueued, [2] counts back (sync), [3] return
-    double host_us[4] = {0, 0, 0, 0};
-    bool direct_counts = true;  // env RSC_DIRECT_COUNTS=0 restores the HBM buffer + D2H copy
-    bool fused_refine = true;   // env RSC_FUSED_REFINE=0: the replay's Refine always as its own launch
-    bool dma_upload = false;    // env RSC_DMA_UPLOAD=1: descriptors by hipMemcpyAsync instead of the copy kernel
-    // eigen stage in the rows form when it has <= W workgroups (small, latency-bound launches such as
-    // one relocalization event: 125 -> 99 us, profiles/r05/bench_latency_forms_ab_r5b.json); env
-    // RSC_EIG_ROWS=W or rsc_context_set_eig_rows overrides (0: lane pairs always)
-    int eig_rows_max_wgs = kEigRowsDefaultWgs;
-    // hypotheses per betas wave for launches small enough for the rows-form eigen stage (a wave runs
-    // the union of its hypotheses' data-dependent chains; env RSC_BETAS_HB)
-    int betas_small_hb = kBetasHyps;
-    // eigen stages beyond the rows form's range: split form (chase and Q rotations on two waves,
-    // pnp_eig_split_kernel; config-2 eigen stage 119 -> 114 us, profiles/r05/split_ab_r5q.jsonl) or
-    // the pair form (env RSC_EIG_SPLIT=0)
-    bool eig_split = true;
-    // host wait for a speculation round's results: spin on a completion flag in pinned host memory
-    // (written by signal_kernel after the round) instead of hipStreamSynchronize's wake-up; env
-    // RSC_SPIN_WAIT=0/1 (stream_wait)
-    bool spin_wait = false;
-    // OptimizeSim3's helper workgroups per pair (the cooperative form; -1: as many as fit one per CU,
-    // at most 7; 0: one workgroup per pair)
-    int so_helpers = -1;
-    DevBuf<char> d_so_coop;  // the cooperative form's hand-off: polled words | publications | lists | chunks
-    uint32_t* h_flag = nullptr;  // [0] stream_wait's sequence flag, [kFaultWord] the eigen stage's fault word
-    uint32_t flag_seq = 0;
-    std::chrono::steady_clock::time_point t_entry;
-};
-
-// The process-global glibc rand() stream the reference draws every sample from (Random.cpp:47-50,
-// Q3): one position shared by all solvers bound to it, advanced by each iterate() call in call order.
-struct rsc_stream {
-    rsc_context* ctx = nullptr;
-    RngStream st;
-    int64_t position = 0;  // draws consumed since srand(seed)
-};
-
-struct rsc_pnp {
-    rsc_context* ctx = nullptr;
-    PnPState st;
-    float4* d_pts = nullptr;
-    float2* d_uv = nullptr;
-    double* d_pws = nullptr;
-    double* d_us = nullptr;
-    double* d_als = nullptr;
-    uint64_t* d_best = nullptr;
-    uint64_t* d_refined = nullptr;
-    int words = 0;
-    int last_kind = 0;  // vbInliers of the last iterate(): 0 empty, 1 refined mask, 2 best mask
-    // position in the last speculation of its context
-    int spec_out0 = -1, spec_H = 0;
-    rsc_stream* stream = nullptr;  // shared rand() stream (rsc_pnp_bind_stream) or null: own stream
-    RngStream own_rng;             // the own stream, parked while bound (st.rng follows the shared one)
-    std::vector<float> h_p2d, h_p3d;  // host copies (the gated events' PoseOptimization problems)
-    ~rsc_pnp() {
-        for (void* p : {(void*)d_pts, (void*)d_uv, (void*)d_pws, (void*)d_us, (void*)d_als, (void*)d_best,
-                        (void*)d_refined})
-            if (p) (void)hipFree(p);
-    }
-};
-
-struct rsc_sim3 {
-    rsc_context* ctx = nullptr;
-    Sim3State st;
-    // prepared arrays (host copies for rsc_sim3_prepared)
-    std::vector<float> X1c, X2c, P1, P2;
-    std::vector<uint64_t> e1, e2;
-    float K1[4], K2[4];
-    float4* d_x1 = nullptr;
-    float4* d_x2 = nullptr;
-    float4* d_pim = nullptr;
-    int spec_out0 = -1, spec_H = 0;
-    rsc_stream* stream = nullptr;
-    RngStream own_rng;
-    ~rsc_sim3() {
-        for (void* p : {(void*)d_x1, (void*)d_x2, (void*)d_pim})
-            if (p) (void)hipFree(p);
-    }
-};
 
 struct rsc_mlpnp {
     rsc_context* ctx = nullptr;
@@ -1246,12 +1038,6 @@ void to_result(const PnPResult& r, rsc_pnp_result* o) {
 // ================================================================================================
 // C ABI
 // ================================================================================================
-// rand() draws per hypothesis: mRansacMinSet RandomInt calls (PnPsolver.cpp:125-131,
-// MLPnPsolver.cpp:84-92), 3 for Sim3 (Sim3Solver.cpp:140-147).
-static inline int draws_per_hypothesis(const PnPState& s) { return s.mRansacMinSet; }
-static inline int draws_per_hypothesis(const Sim3State&) { return 3; }
-static inline int draws_per_hypothesis(const MLState& s) { return s.mRansacMinSet; }
-
 // srand(seed) on a solver's own stream: while the solver is bound, that stream is the parked one
 template <class Solver>
 static void reset_solver(Solver* s, uint32_t seed) {
@@ -1289,95 +1075,6 @@ static int bound_iterate_many(Solver* const* solvers, int count, const int32_t* 
     }
     return RSC_OK;
 }
-
-namespace {
-template <class Solver, class Res, class IterFn>
-int shared_events(Solver* const* solvers, const int32_t* event_begin, int n_events, rsc_stream* const* streams,
-                  Res* per_candidate, rsc_event_result* per_event, IterFn iter, int (*pred_its)(const Solver*)) {
-    if (n_events <= 0) return RSC_OK;
-    if (!solvers || !event_begin || !streams || !per_candidate || !per_event) return RSC_ERR_ARG;
-    const int total = event_begin[n_events];
-    for (int e = 0; e < n_events; ++e) {
-        if (event_begin[e + 1] < event_begin[e] || !streams[e] || streams[e]->ctx != streams[0]->ctx)
-            return RSC_ERR_ARG;
-        for (int f = 0; f < e; ++f)
-            if (streams[f] == streams[e]) return RSC_ERR_ARG;  // one stream per event (calls of two events would interleave)
-        per_event[e] = rsc_event_result{-1, -1, -1, 0};
-    }
-    std::vector<char> discarded(total, 0), resolved(n_events, 0);
-    std::vector<int32_t> start_it(total);
-    std::vector<RngStream> own(total);  // the calls draw from the event's stream; a solver's own
-                                        // stream (st.rng of an unbound one) resumes afterwards
-    for (int i = 0; i < total; ++i) {
-        if (!solvers[i] || solvers[i]->ctx != streams[0]->ctx) return RSC_ERR_ARG;
-        start_it[i] = solvers[i]->st.mnIterations;
-        own[i] = solvers[i]->st.rng;
-    }
-    for (int round = 0;; ++round) {
-        std::vector<Solver*> act;
-        std::vector<int> idx;
-        for (int e = 0; e < n_events; ++e) {
-            if (resolved[e]) continue;
-            RngStream cur = streams[e]->st;  // call positions, assuming every call runs its whole loop
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-                if (discarded[i]) continue;
-                Solver* s = solvers[i];
-                s->st.rng = cur;
-                cur.advance(s->ctx->table, (int64_t)pred_its(s) * draws_per_hypothesis(s->st));
-                act.push_back(s);
-                idx.push_back(i);
-            }
-        }
-        if (act.empty()) break;
-        std::vector<int32_t> its(act.size(), 5), it0(act.size());
-        for (size_t q = 0; q < act.size(); ++q) it0[q] = act[q]->st.mnIterations;
-        std::vector<Res> r(act.size());
-        std::vector<uint8_t*> nomask(act.size(), nullptr);
-        if (int st = iter(act.data(), (int)act.size(), its.data(), r.data(), nomask.data())) return st;
-        std::vector<int> slot(total, -1);
-        for (size_t q = 0; q < act.size(); ++q) slot[idx[q]] = (int)q;
-        for (int e = 0; e < n_events; ++e) {
-            if (resolved[e]) continue;
-            bool any_active = false;
-            int64_t used = 0;
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-                const int q = slot[i];
-                if (q < 0) continue;  // discarded in an earlier round
-                const Solver* s = act[q];
-                used += (int64_t)(s->st.mnIterations - it0[q]) * draws_per_hypothesis(s->st);
-                per_candidate[i] = r[q];
-                if (r[q].no_more) discarded[i] = 1;  // Tracking.cpp:1257-1261, LoopClosing.cpp:292-296
-                if (r[q].ok) {
-                    per_event[e].winner = i - event_begin[e];
-                    per_event[e].round = round;
-                    per_event[e].hypothesis = r[q].iterations - 1 - start_it[i];
-                    per_event[e].n_inliers = r[q].n_inliers;
-                    resolved[e] = 1;
-                    break;
-                }
-                if (!discarded[i]) any_active = true;
-            }
-            streams[e]->st.advance(streams[e]->ctx->table, used);
-            streams[e]->position += used;
-            if (!resolved[e] && !any_active) resolved[e] = 1;
-        }
-    }
-    for (int i = 0; i < total; ++i) solvers[i]->st.rng = own[i];
-    return RSC_OK;
-}
-
-// hypotheses the next iterate(5) call runs unless it succeeds: PnP's '||' loop (Q1)
-// max(5, maxIts - mnIterations), Sim3's '&&' loop min(5, maxIts - mnIterations); none when N is
-// below minInliers (the call returns at once)
-int pnp_pred_its(const rsc_pnp* s) {
-    const PnPState& t = s->st;
-    return (t.N < t.mRansacMinInliers) ? 0 : std::max(0, std::max(5, t.mRansacMaxIts - t.mnIterations));
-}
-int sim3_pred_its(const rsc_sim3* s) {
-    const Sim3State& t = s->st;
-    return (t.N < t.mRansacMinInliers) ? 0 : std::max(0, std::min(5, t.mRansacMaxIts - t.mnIterations));
-}
-}  // namespace
 
 extern "C" {
 
@@ -1565,9 +1262,6 @@ int rsc_pnp_set_ransac_parameters(rsc_pnp* s, double probability, int min_inlier
     return RSC_OK;
 }
 
-static int pnp_iterate_many_impl(rsc_pnp* const* solvers, int count, const int32_t* n_its, rsc_pnp_result* out,
-                                 uint8_t* const* inliers);
-
 int rsc_pnp_iterate_many(rsc_pnp* const* solvers, int count, const int32_t* n_its, rsc_pnp_result* out,
                          uint8_t* const* inliers) {
     if (count <= 0) return RSC_OK;
@@ -1578,7 +1272,7 @@ int rsc_pnp_iterate_many(rsc_pnp* const* solvers, int count, const int32_t* n_it
     return pnp_iterate_many_impl(solvers, count, n_its, out, inliers);
 }
 
-static int pnp_iterate_many_impl(rsc_pnp* const* solvers, int count, const int32_t* n_its, rsc_pnp_result* out,
+int pnp_iterate_many_impl(rsc_pnp* const* solvers, int count, const int32_t* n_its, rsc_pnp_result* out,
                                  uint8_t* const* inliers) {
     if (count <= 0) return RSC_OK;
     if (!solvers || !n_its || !out) return RSC_ERR_ARG;
@@ -1751,9 +1445,6 @@ int rsc_sim3_set_ransac_parameters(rsc_sim3* s, double probability, int min_inli
     return RSC_OK;
 }
 
-static int sim3_iterate_many_impl(rsc_sim3* const* solvers, int count, const int32_t* n_its, rsc_sim3_result* out,
-                                  uint8_t* const* inliers);
-
 int rsc_sim3_iterate_many(rsc_sim3* const* solvers, int count, const int32_t* n_its, rsc_sim3_result* out,
                           uint8_t* const* inliers) {
     if (count <= 0) return RSC_OK;
@@ -1764,7 +1455,7 @@ int rsc_sim3_iterate_many(rsc_sim3* const* solvers, int count, const int32_t* n_
     return sim3_iterate_many_impl(solvers, count, n_its, out, inliers);
 }
 
-static int sim3_iterate_many_impl(rsc_sim3* const* solvers, int count, const int32_t* n_its, rsc_sim3_result* out,
+int sim3_iterate_many_impl(rsc_sim3* const* solvers, int count, const int32_t* n_its, rsc_sim3_result* out,
                                   uint8_t* const* inliers) {
     if (count <= 0) return RSC_OK;
     if (!solvers || !n_its || !out) return RSC_ERR_ARG;
@@ -1838,7 +1529,6 @@ int rsc_sim3_prepared(const rsc_sim3* s, float* X1c, float* X2c, float* P1im1, f
     if (idx) std::memcpy(idx, s->st.indices1.data(), 4 * (size_t)N);
     return RSC_OK;
 }
-
 
 // ---- Optimizer::PoseOptimization (src/Optimizer.cpp:205-424) ----
 int rsc_pose_optimization_many(rsc_context* C, const rsc_poseopt_problem* P, int count, rsc_poseopt_result* out,
@@ -2607,7 +2297,6 @@ int rsc_bow_create_transformed(rsc_context* C, rsc_voc* V, const rsc_bow_feature
     return RSC_OK;
 }
 
-
 // ---- ORBmatcher::SearchBySim3 (src/ORBmatcher.cpp:948-1170) ----
 namespace {
 struct S3Blob {
@@ -2651,22 +2340,6 @@ int check_sim3_kf(const rsc_sim3_kf& k) {
     return 0;
 }
 }  // namespace
-
-struct rsc_kfview {
-    rsc_context* ctx = nullptr;
-    int n = 0;
-    DevBuf<char> mem;  // DevSim3KF header | kp | octave | desc | grid | scales | MapPoints
-    const DevSim3KF* hdr = nullptr;
-    // host copies of what OptimizeSim3 reads (the gated loop events build its problem from them)
-    std::vector<float> kp, mp_pos, inv_level_sigma2;
-    std::vector<int32_t> octave;
-    std::vector<uint8_t> mp_state;
-    float R[9], t[3], K[4];
-    float top_scale = 1.0f;  // mvScaleFactors[n_levels - 1] (the largest search radius is th times it)
-    DevSim3KF dev;           // the header as uploaded (device pointers), for SearchByProjection's problem table
-    DevBuf<float> d_angle;   // mvKeysUn[i].angle (rsc_kfview_set_angles)
-    bool has_angles = false;
-};
 
 int rsc_kfview_create(rsc_context* C, const rsc_sim3_kf* k, rsc_kfview** out) {
     if (!C || !k || !out) return RSC_ERR_ARG;
@@ -2832,22 +2505,6 @@ int rsc_diag_sim3match_directions(rsc_context* C, int pair, int32_t* m1, int n1,
 }
 
 // ---- ORBmatcher::SearchByProjection(Frame&, KeyFrame, sAlreadyFound, th, ORBdist) (rsc_frameproj.h) ----
-struct rsc_frameview {
-    rsc_context* ctx = nullptr;
-    int n = 0;
-    DevBuf<char> mem;  // DevProjFrame header | kp | octave | angle | desc | grid | scales
-    const DevProjFrame* hdr = nullptr;
-    // host copies of what the refinement chain's PoseOptimization problems read
-    std::vector<float> kp, inv_level_sigma2;
-    std::vector<int32_t> octave;
-    float K[4];
-    DevBuf<float> d_uright;  // mvuRight (rsc_frameview_set_stereo)
-    std::vector<float> h_uright;  // its host copy (the motion-model driver's PoseOptimization problems)
-    float mbf = 0.0f;
-    bool has_stereo = false;
-    float top_scale = 1.0f, gw_inv = 0.0f, gh_inv = 0.0f;  // the radius guard of the last-frame matcher
-};
-
 int rsc_frameview_create(rsc_context* C, const rsc_frame_features* f, rsc_frameview** out) {
     if (!C || !f || !out) return RSC_ERR_ARG;
     *out = nullptr;
@@ -3025,141 +2682,6 @@ int rsc_search_by_projection_many(rsc_context* C, rsc_frameview* const* frames, 
         if (rounds) std::memcpy(&rounds[c], h + o_cnt[c] + 4, 4);
     }
     return RSC_OK;
-}
-
-// Tracking::Relocalization's refinement chain (Tracking.cpp:1294-1323); each stage one launch over the
-// candidates still in the chain.
-int rsc_reloc_refine_many(rsc_context* C, rsc_frameview* const* frames, rsc_kfview* const* kfs, int count,
-                          const rsc_reloc_frame* fr, int32_t* const* frame_mp, const uint8_t* const* found,
-                          const int32_t* n_good_in, const float* Tcw_in, rsc_reloc_refine_result* out) {
-    if (!C || count < 0) return RSC_ERR_ARG;
-    if (count == 0) return RSC_OK;
-    if (!frames || !kfs || !fr || !frame_mp || !found || !n_good_in || !Tcw_in || !out) return RSC_ERR_ARG;
-    for (int c = 0; c < count; ++c) {
-        if (!frames[c] || !kfs[c] || frames[c]->ctx != C || kfs[c]->ctx != C) return RSC_ERR_ARG;
-        if ((frames[c]->n && !frame_mp[c]) || (kfs[c]->n && !found[c])) return RSC_ERR_ARG;
-        for (int f = 0; f < frames[c]->n; ++f)
-            if (frame_mp[c][f] < -1 || frame_mp[c][f] >= kfs[c]->n) return RSC_ERR_ARG;
-        rsc_reloc_refine_result& r = out[c];
-        r.n_good = n_good_in[c];
-        r.n_additional[0] = r.n_additional[1] = -1;
-        r.pose_opts = 0;
-        std::memcpy(r.Tcw, Tcw_in + 16 * (size_t)c, sizeof(r.Tcw));
-    }
-    // SearchByProjection over the candidates in `sel` with sAlreadyFound = fnd[c]; the new matches are
-    // written to frame_mp (CurrentFrame.mvpMapPoints[bestIdx2] = pMP), nadd[c] = the return value
-    std::vector<int32_t> nadd(count, 0);
-    auto search = [&](const std::vector<int>& sel, const std::vector<const uint8_t*>& fnd, float th, int orb_dist) -> int {
-        const int m = (int)sel.size();
-        std::vector<rsc_frameview*> F(m);
-        std::vector<rsc_kfview*> K(m);
-        std::vector<float> T(16 * (size_t)m);
-        std::vector<const int32_t*> mp(m);
-        std::vector<std::vector<int32_t>> res(m);
-        std::vector<int32_t*> rp(m);
-        std::vector<int32_t> nm(m);
-        for (int q = 0; q < m; ++q) {
-            const int c = sel[q];
-            F[q] = frames[c];
-            K[q] = kfs[c];
-            std::memcpy(&T[16 * (size_t)q], out[c].Tcw, 16 * sizeof(float));
-            mp[q] = frame_mp[c];
-            res[q].assign((size_t)std::max(frames[c]->n, 1), -1);
-            rp[q] = res[q].data();
-        }
-        if (int st = rsc_search_by_projection_many(C, F.data(), K.data(), m, T.data(), fnd.data(), mp.data(), th,
-                                                   orb_dist, 1, rp.data(), nm.data(), nullptr))
-            return st;
-        for (int q = 0; q < m; ++q) {
-            const int c = sel[q];
-            for (int f = 0; f < frames[c]->n; ++f)
-                if (res[q][f] >= 0) frame_mp[c][f] = res[q][f];
-            nadd[c] = nm[q];
-        }
-        return RSC_OK;
-    };
-    // PoseOptimization(&mCurrentFrame) over the candidates in `sel`, on every occupied slot
-    auto optimise = [&](const std::vector<int>& sel, bool null_outliers) -> int {
-        const int m = (int)sel.size();
-        std::vector<std::vector<uint8_t>> has(m), outl(m);
-        std::vector<std::vector<float>> Xw(m), inv(m);
-        std::vector<rsc_poseopt_problem> pr(m);
-        std::vector<rsc_poseopt_result> res(m);
-        std::vector<uint8_t*> op(m);
-        for (int q = 0; q < m; ++q) {
-            const int c = sel[q];
-            const rsc_frameview& F = *frames[c];
-            const rsc_kfview& K = *kfs[c];
-            const size_t n = (size_t)F.n;
-            has[q].assign(std::max(n, (size_t)1), 0);
-            outl[q].assign(std::max(n, (size_t)1), 0);
-            Xw[q].assign(3 * std::max(n, (size_t)1), 0.f);
-            inv[q].assign(std::max(n, (size_t)1), 0.f);
-            for (size_t f = 0; f < n; ++f) {
-                const int32_t s = frame_mp[c][f];
-                if (s < 0) continue;
-                has[q][f] = 1;
-                for (int k = 0; k < 3; ++k) Xw[q][3 * f + k] = K.mp_pos[3 * (size_t)s + k];
-                inv[q][f] = F.inv_level_sigma2[F.octave[f]];
-            }
-            rsc_poseopt_problem& P = pr[q];
-            P.n = F.n;
-            P.has_mp = has[q].data();
-            P.uv = F.kp.data();
-            P.Xw = Xw[q].data();
-            P.inv_sigma2 = inv[q].data();
-            P.u_right = fr[c].u_right;
-            P.fx = F.K[0]; P.fy = F.K[1]; P.cx = F.K[2]; P.cy = F.K[3];
-            std::memcpy(P.Tcw, out[c].Tcw, sizeof(P.Tcw));
-            P.bf = fr[c].bf;
-            op[q] = outl[q].data();
-        }
-        if (int st = rsc_pose_optimization_many(C, pr.data(), m, res.data(), op.data())) return st;
-        for (int q = 0; q < m; ++q) {
-            const int c = sel[q];
-            out[c].n_good = res[q].n_good;
-            std::memcpy(out[c].Tcw, res[q].Tcw, sizeof(out[c].Tcw));
-            out[c].pose_opts++;
-            if (null_outliers)  // :1317-1319
-                for (int f = 0; f < frames[c]->n; ++f)
-                    if (has[q][f] && outl[q][f]) frame_mp[c][f] = -1;
-        }
-        return RSC_OK;
-    };
-    std::vector<int> s1, s2, s3, s4;
-    std::vector<const uint8_t*> f1;
-    for (int c = 0; c < count; ++c)
-        if (out[c].n_good < 50) {  // :1294
-            s1.push_back(c);
-            f1.push_back(found[c]);
-        }
-    if (s1.empty()) return RSC_OK;
-    if (int st = search(s1, f1, 10.0f, 100)) return st;  // :1296
-    for (int c : s1) {
-        out[c].n_additional[0] = nadd[c];
-        if (nadd[c] + out[c].n_good >= 50) s2.push_back(c);  // :1298
-    }
-    if (s2.empty()) return RSC_OK;
-    if (int st = optimise(s2, false)) return st;  // :1300
-    std::vector<std::vector<uint8_t>> found2;
-    for (int c : s2)
-        if (out[c].n_good > 30 && out[c].n_good < 50) {  // :1304
-            s3.push_back(c);
-            std::vector<uint8_t> fnd((size_t)std::max(kfs[c]->n, 1), 0);  // :1306-1309
-            for (int f = 0; f < frames[c]->n; ++f)
-                if (frame_mp[c][f] >= 0) fnd[frame_mp[c][f]] = 1;
-            found2.push_back(std::move(fnd));
-        }
-    if (s3.empty()) return RSC_OK;
-    std::vector<const uint8_t*> f3;
-    for (const auto& v : found2) f3.push_back(v.data());
-    if (int st = search(s3, f3, 3.0f, 64)) return st;  // :1310
-    for (int c : s3) {
-        out[c].n_additional[1] = nadd[c];
-        if (out[c].n_good + nadd[c] >= 50) s4.push_back(c);  // :1313
-    }
-    if (s4.empty()) return RSC_OK;
-    return optimise(s4, true);  // :1315-1319
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3805,620 +3327,6 @@ int rsc_mlpnp_last_samples(rsc_mlpnp* s, int32_t* out, int cap) {
     return n;
 }
 
-// ---- Event drivers (config 5) ----
-int rsc_reloc_events(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events, rsc_pnp_result* per_candidate,
-                     rsc_event_result* per_event) {
-    if (n_events <= 0) return RSC_OK;
-    if (!solvers || !event_begin || !per_candidate || !per_event) return RSC_ERR_ARG;
-    const int total = event_begin[n_events];
-    for (int e = 0; e < n_events; ++e) {
-        if (event_begin[e + 1] < event_begin[e]) return RSC_ERR_ARG;
-        per_event[e] = rsc_event_result{-1, -1, -1, 0};
-    }
-    std::vector<char> discarded(total, 0), resolved(n_events, 0);
-    std::vector<int32_t> start_it(total);
-    for (int i = 0; i < total; ++i) {
-        if (!solvers[i]) return RSC_ERR_ARG;
-        start_it[i] = solvers[i]->st.mnIterations;
-    }
-    for (int round = 0;; ++round) {
-        std::vector<rsc_pnp*> act;
-        std::vector<int> idx;
-        for (int e = 0; e < n_events; ++e) {
-            if (resolved[e]) continue;
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i)
-                if (!discarded[i]) { act.push_back(solvers[i]); idx.push_back(i); }
-        }
-        if (act.empty()) break;
-        std::vector<int32_t> its(act.size(), 5);
-        std::vector<rsc_pnp_result> r(act.size());
-        std::vector<uint8_t*> nomask(act.size(), nullptr);
-        if (int st = rsc_pnp_iterate_many(act.data(), (int)act.size(), its.data(), r.data(), nomask.data())) return st;
-        std::vector<char> iterated(total, 0);
-        for (size_t q = 0; q < act.size(); ++q) {
-            iterated[idx[q]] = 1;
-            per_candidate[idx[q]] = r[q];
-            if (r[q].no_more) discarded[idx[q]] = 1;  // Tracking.cpp:1257-1261
-        }
-        for (int e = 0; e < n_events; ++e) {
-            if (resolved[e]) continue;
-            bool any_active = false;
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-                if (!iterated[i]) continue;  // candidates iterated this round, in order
-                if (per_candidate[i].ok) {
-                    per_event[e].winner = i - event_begin[e];
-                    per_event[e].round = round;
-                    per_event[e].hypothesis = per_candidate[i].iterations - 1 - start_it[i];
-                    per_event[e].n_inliers = per_candidate[i].n_inliers;
-                    resolved[e] = 1;
-                    break;
-                }
-                if (!discarded[i]) any_active = true;
-            }
-            if (!resolved[e] && !any_active) resolved[e] = 1;
-        }
-    }
-    return RSC_OK;
-}
-
-int rsc_loop_events(rsc_sim3* const* solvers, const int32_t* event_begin, int n_events,
-                    rsc_sim3_result* per_candidate, rsc_event_result* per_event) {
-    if (n_events <= 0) return RSC_OK;
-    if (!solvers || !event_begin || !per_candidate || !per_event) return RSC_ERR_ARG;
-    const int total = event_begin[n_events];
-    std::vector<int32_t> its(total), start_it(total);
-    for (int i = 0; i < total; ++i) {
-        if (!solvers[i]) return RSC_ERR_ARG;
-        start_it[i] = solvers[i]->st.mnIterations;
-        its[i] = std::max(1, solvers[i]->st.mRansacMaxIts - solvers[i]->st.mnIterations);
-    }
-    std::vector<uint8_t*> nomask(total, nullptr);
-    if (total > 0)
-        if (int st = rsc_sim3_iterate_many(solvers, total, its.data(), per_candidate, nomask.data())) return st;
-    for (int e = 0; e < n_events; ++e) {
-        per_event[e] = rsc_event_result{-1, -1, -1, 0};
-        int best_round = 0;
-        for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-            if (!per_candidate[i].ok) continue;
-            const int h = per_candidate[i].iterations - 1 - start_it[i];
-            const int round = h / 5;
-            if (per_event[e].winner < 0 || round < best_round) {
-                best_round = round;
-                per_event[e] = rsc_event_result{i - event_begin[e], round, h, per_candidate[i].n_inliers};
-            }
-        }
-    }
-    return RSC_OK;
-}
-
-// ---- Events on the reference's shared rand() stream (Q3) ----
-// One round of the round-robin: every live candidate of every unresolved event runs iterate(5) in
-// one set of launches.  A candidate's call starts where the previous candidate's call of its event
-// ended, assuming every call runs its whole loop; the only call that ends early is a success, which
-// resolves the event (Tracking.cpp:1284-1331 / LoopClosing.cpp:311-327 with the gate passed), so the
-// candidates after it in that round are calls the reference never makes: their records are
-// discarded (left as they were before the round) and the stream advances by the calls made.
-
-int rsc_reloc_events_shared(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events,
-                            rsc_stream* const* streams, rsc_pnp_result* per_candidate, rsc_event_result* per_event) {
-    for (int i = 0; n_events > 0 && solvers && event_begin && i < event_begin[n_events]; ++i)
-        if (solvers[i] && solvers[i]->stream) return RSC_ERR_ARG;  // events position their own calls
-    return shared_events(solvers, event_begin, n_events, streams, per_candidate, per_event, pnp_iterate_many_impl,
-                         pnp_pred_its);
-}
-
-int rsc_loop_events_shared(rsc_sim3* const* solvers, const int32_t* event_begin, int n_events,
-                           rsc_stream* const* streams, rsc_sim3_result* per_candidate, rsc_event_result* per_event) {
-    for (int i = 0; n_events > 0 && solvers && event_begin && i < event_begin[n_events]; ++i)
-        if (solvers[i] && solvers[i]->stream) return RSC_ERR_ARG;
-    return shared_events(solvers, event_begin, n_events, streams, per_candidate, per_event, sim3_iterate_many_impl,
-                         sim3_pred_its);
-}
-
-// ---- Gated events (round 6) ----
-// Tracking::Relocalization (Tracking.cpp:1239-1335): each round runs iterate(5) on every live
-// candidate of every unresolved event in one set of launches (own streams: the results are the
-// reference's calls whatever happens before them in the round), then walks each event's successes in
-// candidate order: PoseOptimization on the success (mCurrentFrame.mvpMapPoints = the inlier matches,
-// mTcw = the RANSAC pose, :1268-1284), nGood < 10 -> the next success of the round (:1286-1287),
-// nGood >= 50 -> match (:1327-1331), otherwise SearchByProjection's turn (handed off).  The gate
-// passes of all events run as one rsc_pose_optimization_many each.
-//
-// rsc_reloc_events_refined is the same loop with `refine` set: a success with 10 <= nGood < 50 goes
-// through the SearchByProjection chain (rsc_reloc_refine_many over the events of the pass) and is a match
-// when that leaves nGood >= 50; otherwise the walk continues with the event's next success (:1327-1333).
-namespace {
-struct RelocRefine {
-    const rsc_reloc_candidate* cands;
-    rsc_frameview* const* views;
-    rsc_reloc_refined_result* per_event;
-    int32_t* const* frame_mp_out;
-};
-
-int reloc_events_gated_impl(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events,
-                            const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
-                            rsc_reloc_gate_result* per_event, uint8_t* const* outlier, uint8_t* const* inliers,
-                            const RelocRefine* refine) {
-    if (n_events <= 0) return RSC_OK;
-    if (!solvers || !event_begin || !frames || !per_candidate || !per_event) return RSC_ERR_ARG;
-    const int total = event_begin[n_events];
-    rsc_context* C = nullptr;
-    for (int e = 0; e < n_events; ++e) {
-        if (event_begin[e + 1] < event_begin[e] || event_begin[e] < 0) return RSC_ERR_ARG;
-        rsc_reloc_gate_result& r = per_event[e];
-        std::memset(&r, 0, sizeof(r));
-        r.status = RSC_GATE_NONE;
-        r.winner = r.round = r.hypothesis = -1;
-        for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-            if (!solvers[i]) return RSC_ERR_ARG;
-            if (solvers[i]->stream) return RSC_ERR_UNSUPPORTED;  // gating moves later calls' stream positions
-            if (!C) C = solvers[i]->ctx;
-            // one Frame per event: every candidate's vbInliers indexes the same mCurrentFrame slots
-            if (solvers[i]->ctx != C || solvers[i]->st.N_points != solvers[event_begin[e]]->st.N_points)
-                return RSC_ERR_ARG;
-        }
-    }
-    if (!C) return RSC_OK;
-    std::vector<char> discarded(total, 0), resolved(n_events, 0);
-    std::vector<int32_t> start_it(total);
-    std::vector<std::vector<uint8_t>> mask(total);
-    for (int i = 0; i < total; ++i) {
-        start_it[i] = solvers[i]->st.mnIterations;
-        mask[i].assign((size_t)std::max(solvers[i]->st.N_points, 1), 0);
-    }
-    // per gate job: the PoseOptimization problem's slot arrays (Frame::N slots)
-    struct Job {
-        int e, i;
-        std::vector<uint8_t> has_mp, outl;
-        std::vector<float> uv, Xw, inv;
-    };
-    for (int round = 0;; ++round) {
-        std::vector<rsc_pnp*> act;
-        std::vector<int> idx;
-        for (int e = 0; e < n_events; ++e) {
-            if (resolved[e]) continue;
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i)
-                if (!discarded[i]) { act.push_back(solvers[i]); idx.push_back(i); }
-        }
-        if (act.empty()) break;
-        std::vector<int32_t> its(act.size(), 5);
-        std::vector<rsc_pnp_result> r(act.size());
-        std::vector<uint8_t*> mp(act.size());
-        for (size_t q = 0; q < act.size(); ++q) mp[q] = mask[idx[q]].data();
-        if (int st = rsc_pnp_iterate_many(act.data(), (int)act.size(), its.data(), r.data(), mp.data())) return st;
-        std::vector<char> iterated(total, 0);
-        for (size_t q = 0; q < act.size(); ++q) {
-            iterated[idx[q]] = 1;
-            per_candidate[idx[q]] = r[q];
-            if (r[q].no_more) discarded[idx[q]] = 1;  // Tracking.cpp:1257-1261
-        }
-        // gate passes: each unresolved event's next success of this round, in candidate order
-        std::vector<int> cursor(n_events);
-        for (int e = 0; e < n_events; ++e) cursor[e] = event_begin[e];
-        for (;;) {
-            std::vector<Job> jobs;
-            for (int e = 0; e < n_events; ++e) {
-                if (resolved[e]) continue;
-                int i = cursor[e];
-                while (i < event_begin[e + 1] && !(iterated[i] && per_candidate[i].ok)) ++i;
-                cursor[e] = i + 1;
-                if (i >= event_begin[e + 1]) continue;
-                const rsc_pnp* s = solvers[i];
-                const PnPState& st = s->st;
-                const int nf = st.N_points;
-                Job j;
-                j.e = e;
-                j.i = i;
-                j.has_mp.assign((size_t)nf, 0);
-                j.outl.assign((size_t)nf, 0);
-                j.uv.assign(2 * (size_t)nf, 0.f);
-                j.Xw.assign(3 * (size_t)nf, 0.f);
-                j.inv.assign((size_t)nf, 0.f);
-                for (int c = 0; c < st.N; ++c) {
-                    const int slot = st.kp_index[c];
-                    if (!mask[i][slot]) continue;  // mvpMapPoints[j] = inlier ? match : NULL (:1276-1282)
-                    j.has_mp[slot] = 1;
-                    j.uv[2 * slot] = s->h_p2d[2 * c];
-                    j.uv[2 * slot + 1] = s->h_p2d[2 * c + 1];
-                    for (int k = 0; k < 3; ++k) j.Xw[3 * slot + k] = s->h_p3d[3 * c + k];
-                    j.inv[slot] = 1.0f / st.sigma2[c];  // mvInvLevelSigma2 = 1.0f / mvLevelSigma2
-                }
-                jobs.push_back(std::move(j));
-            }
-            if (jobs.empty()) break;
-            std::vector<rsc_poseopt_problem> pr(jobs.size());
-            std::vector<rsc_poseopt_result> res(jobs.size());
-            std::vector<uint8_t*> op(jobs.size());
-            for (size_t q = 0; q < jobs.size(); ++q) {
-                const Job& j = jobs[q];
-                const PnPState& st = solvers[j.i]->st;
-                rsc_poseopt_problem& P = pr[q];
-                P.n = st.N_points;
-                P.has_mp = j.has_mp.data();
-                P.uv = j.uv.data();
-                P.Xw = j.Xw.data();
-                P.inv_sigma2 = j.inv.data();
-                P.u_right = frames[j.e].u_right;
-                P.fx = st.fx; P.fy = st.fy; P.cx = st.cx; P.cy = st.cy;
-                std::memcpy(P.Tcw, per_candidate[j.i].T, sizeof(P.Tcw));
-                P.bf = frames[j.e].bf;
-                op[q] = jobs[q].outl.data();
-            }
-            if (int st = rsc_pose_optimization_many(C, pr.data(), (int)pr.size(), res.data(), op.data())) return st;
-            struct Chain {
-                size_t q;  // its job
-                std::vector<int32_t> mp;
-                std::vector<uint8_t> found;
-            };
-            std::vector<Chain> chains;
-            for (size_t q = 0; q < jobs.size(); ++q) {
-                const Job& j = jobs[q];
-                rsc_reloc_gate_result& g = per_event[j.e];
-                g.gates++;
-                const int nGood = res[q].n_good;
-                if (nGood < 10) {  // Tracking.cpp:1286-1287: continue with the next candidate
-                    g.rejected++;
-                    continue;
-                }
-                if (refine) {
-                    // mvpMapPoints after :1289-1291 as KeyFrame slots, and sFound (:1278, every inlier)
-                    const rsc_pnp* s = solvers[j.i];
-                    const rsc_reloc_candidate& cd = refine->cands[j.i];
-                    Chain ch;
-                    ch.q = q;
-                    ch.mp.assign((size_t)std::max(s->st.N_points, 1), -1);
-                    ch.found.assign((size_t)std::max(cd.kf->n, 1), 0);
-                    for (int c = 0; c < s->st.N; ++c) {
-                        const int slot = s->st.kp_index[c];
-                        if (!mask[j.i][slot]) continue;
-                        const int32_t ks = cd.matches[slot];
-                        if (ks < 0 || ks >= cd.kf->n) {
-                            g_last_error = "a RANSAC inlier's Frame slot has no KeyFrame slot in the candidate's matches";
-                            return RSC_ERR_ARG;
-                        }
-                        ch.found[ks] = 1;
-                        if (!j.outl[slot]) ch.mp[slot] = ks;
-                    }
-                    rsc_reloc_refined_result& x = refine->per_event[j.e];
-                    if (nGood < 50) {  // :1294: the chain decides
-                        chains.push_back(std::move(ch));
-                        continue;
-                    }
-                    x.n_good_first = nGood;
-                    x.n_additional[0] = x.n_additional[1] = -1;
-                    if (refine->frame_mp_out && refine->frame_mp_out[j.e])
-                        std::memcpy(refine->frame_mp_out[j.e], ch.mp.data(), 4 * (size_t)s->st.N_points);
-                }
-                g.status = nGood >= 50 ? RSC_GATE_MATCH : RSC_GATE_HANDOFF;
-                g.winner = j.i - event_begin[j.e];
-                g.round = round;
-                g.hypothesis = per_candidate[j.i].iterations - 1 - start_it[j.i];
-                g.n_inliers = per_candidate[j.i].n_inliers;
-                g.n_good = nGood;
-                std::memcpy(g.Tcw, res[q].Tcw, sizeof(g.Tcw));
-                const int nf = solvers[j.i]->st.N_points;
-                if (outlier && outlier[j.e]) std::memcpy(outlier[j.e], j.outl.data(), (size_t)nf);
-                if (inliers && inliers[j.e]) std::memcpy(inliers[j.e], mask[j.i].data(), (size_t)nf);
-                resolved[j.e] = 1;
-            }
-            if (!chains.empty()) {  // Tracking.cpp:1294-1323 on this pass's successes with 10 <= nGood < 50
-                const size_t m = chains.size();
-                std::vector<rsc_frameview*> F(m);
-                std::vector<rsc_kfview*> K(m);
-                std::vector<rsc_reloc_frame> fr(m);
-                std::vector<int32_t*> mp(m);
-                std::vector<const uint8_t*> fnd(m);
-                std::vector<int32_t> ng(m);
-                std::vector<float> T(16 * m);
-                std::vector<rsc_reloc_refine_result> rr(m);
-                for (size_t k = 0; k < m; ++k) {
-                    const Job& j = jobs[chains[k].q];
-                    F[k] = refine->views[j.e];
-                    K[k] = refine->cands[j.i].kf;
-                    fr[k] = frames[j.e];
-                    mp[k] = chains[k].mp.data();
-                    fnd[k] = chains[k].found.data();
-                    ng[k] = res[chains[k].q].n_good;
-                    std::memcpy(&T[16 * k], res[chains[k].q].Tcw, 16 * sizeof(float));
-                }
-                if (int st = rsc_reloc_refine_many(C, F.data(), K.data(), (int)m, fr.data(), mp.data(), fnd.data(),
-                                                   ng.data(), T.data(), rr.data()))
-                    return st;
-                for (size_t k = 0; k < m; ++k) {
-                    const Job& j = jobs[chains[k].q];
-                    rsc_reloc_gate_result& g = per_event[j.e];
-                    rsc_reloc_refined_result& x = refine->per_event[j.e];
-                    x.chains++;
-                    if (rr[k].n_good < 50) {  // :1327 fails: the next success of the round
-                        g.rejected++;
-                        continue;
-                    }
-                    g.status = RSC_GATE_MATCH;
-                    g.winner = j.i - event_begin[j.e];
-                    g.round = round;
-                    g.hypothesis = per_candidate[j.i].iterations - 1 - start_it[j.i];
-                    g.n_inliers = per_candidate[j.i].n_inliers;
-                    g.n_good = rr[k].n_good;
-                    std::memcpy(g.Tcw, rr[k].Tcw, sizeof(g.Tcw));
-                    x.n_good_first = ng[k];
-                    x.n_additional[0] = rr[k].n_additional[0];
-                    x.n_additional[1] = rr[k].n_additional[1];
-                    const int nf = solvers[j.i]->st.N_points;
-                    if (refine->frame_mp_out && refine->frame_mp_out[j.e])
-                        std::memcpy(refine->frame_mp_out[j.e], chains[k].mp.data(), 4 * (size_t)nf);
-                    if (inliers && inliers[j.e]) std::memcpy(inliers[j.e], mask[j.i].data(), (size_t)nf);
-                    resolved[j.e] = 1;
-                }
-            }
-        }
-        for (int e = 0; e < n_events; ++e) {  // nCandidates == 0: the while loop ends (:1239)
-            if (resolved[e]) continue;
-            bool any_active = false;
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) any_active |= !discarded[i];
-            if (!any_active) resolved[e] = 1;
-        }
-    }
-    return RSC_OK;
-}
-}  // namespace
-
-int rsc_reloc_events_gated(rsc_pnp* const* solvers, const int32_t* event_begin, int n_events,
-                           const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
-                           rsc_reloc_gate_result* per_event, uint8_t* const* outlier, uint8_t* const* inliers) {
-    return reloc_events_gated_impl(solvers, event_begin, n_events, frames, per_candidate, per_event, outlier,
-                                   inliers, nullptr);
-}
-
-int rsc_reloc_events_refined(rsc_pnp* const* solvers, const rsc_reloc_candidate* candidates,
-                             const int32_t* event_begin, int n_events, rsc_frameview* const* views,
-                             const rsc_reloc_frame* frames, rsc_pnp_result* per_candidate,
-                             rsc_reloc_refined_result* per_event, int32_t* const* frame_mp_out) {
-    if (n_events <= 0) return RSC_OK;
-    if (!solvers || !candidates || !event_begin || !views || !frames || !per_candidate || !per_event)
-        return RSC_ERR_ARG;
-    for (int e = 0; e < n_events; ++e) {
-        if (event_begin[e + 1] < event_begin[e] || event_begin[e] < 0) return RSC_ERR_ARG;
-        if (event_begin[e + 1] > event_begin[e] && !views[e]) return RSC_ERR_ARG;
-        for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-            if (!solvers[i] || !candidates[i].kf || !candidates[i].matches) return RSC_ERR_ARG;
-            if (solvers[i]->st.N_points != views[e]->n || candidates[i].kf->ctx != solvers[i]->ctx ||
-                views[e]->ctx != solvers[i]->ctx)
-                return RSC_ERR_ARG;
-            if (!candidates[i].kf->has_angles) return RSC_ERR_ARG;  // matcher2(0.9, true) checks orientation
-        }
-        std::memset(&per_event[e], 0, sizeof(per_event[e]));
-        per_event[e].n_additional[0] = per_event[e].n_additional[1] = -1;
-    }
-    std::vector<rsc_reloc_gate_result> g((size_t)n_events);
-    const RelocRefine rf{candidates, views, per_event, frame_mp_out};
-    const int st = reloc_events_gated_impl(solvers, event_begin, n_events, frames, per_candidate, g.data(), nullptr,
-                                           nullptr, &rf);
-    if (st) return st;
-    for (int e = 0; e < n_events; ++e) {
-        rsc_reloc_refined_result& x = per_event[e];
-        x.status = g[e].status;
-        x.winner = g[e].winner;
-        x.round = g[e].round;
-        x.hypothesis = g[e].hypothesis;
-        x.n_inliers = g[e].n_inliers;
-        x.n_good = g[e].n_good;
-        x.rejected = g[e].rejected;
-        x.gates = g[e].gates;
-        std::memcpy(x.Tcw, g[e].Tcw, sizeof(x.Tcw));
-    }
-    return RSC_OK;
-}
-
-// LoopClosing::ComputeSim3 (LoopClosing.cpp:268-329): a candidate's k-th success comes back from the
-// call that reaches it (Sim3Solver::iterate returns at the first hypothesis with more than
-// mRansacMinInliers inliers, Sim3Solver.cpp:155-163), so with its own stream each candidate's
-// successes are computed one at a time, each with the whole remaining budget in one call, and placed
-// in the round-robin: a call starting at hypothesis p in round c covers p..p+4, so the success at
-// hypothesis s is returned in round c + (s - p) / 5 and the next call starts at s + 1 in the round
-// after.  The event takes its successes in (round, candidate) order: SearchBySim3(7.5) on the inliers
-// (:296-309), OptimizeSim3(gScm = Sim3(R, t, 1), 10) (:310-311), accepted when nInliers >= 20
-// (:314-325); a rejected candidate's next success is computed and the walk goes on.  Each pass gates
-// one success per unresolved event (one launch of each stage over all of them).
-int rsc_loop_events_gated(rsc_sim3* const* solvers, const rsc_loop_candidate* cands, const int32_t* event_begin,
-                          int n_events, rsc_sim3_result* per_candidate, rsc_loop_gate_result* per_event,
-                          int32_t* const* matches_out) {
-    if (n_events <= 0) return RSC_OK;
-    if (!solvers || !cands || !event_begin || !per_candidate || !per_event) return RSC_ERR_ARG;
-    const int total = event_begin[n_events];
-    rsc_context* C = nullptr;
-    for (int e = 0; e < n_events; ++e) {
-        if (event_begin[e + 1] < event_begin[e] || event_begin[e] < 0) return RSC_ERR_ARG;
-        rsc_loop_gate_result& r = per_event[e];
-        std::memset(&r, 0, sizeof(r));
-        r.status = RSC_GATE_NONE;
-        r.winner = r.round = r.hypothesis = -1;
-        for (int i = event_begin[e]; i < event_begin[e + 1]; ++i) {
-            const rsc_loop_candidate& k = cands[i];
-            if (!solvers[i] || !k.kf1 || !k.kf2) return RSC_ERR_ARG;
-            if (solvers[i]->stream) return RSC_ERR_UNSUPPORTED;
-            if (!C) C = solvers[i]->ctx;
-            if (solvers[i]->ctx != C || k.kf1->ctx != C || k.kf2->ctx != C) return RSC_ERR_ARG;
-            if (solvers[i]->st.mN1 != k.kf1->n || (k.kf1->n > 0 && !k.matches12)) return RSC_ERR_ARG;
-            if (k.kf1 != cands[event_begin[e]].kf1) return RSC_ERR_ARG;  // one mpCurrentKF per event
-            for (int a = 0; a < k.kf1->n; ++a)
-                if (k.matches12[a] < -2 || k.matches12[a] >= k.kf2->n) return RSC_ERR_ARG;
-        }
-    }
-    if (!C) return RSC_OK;
-    std::vector<int32_t> start_it(total), pos(total), calls(total, 0), s_round(total, -1);
-    std::vector<std::vector<uint8_t>> mask(total);
-    for (int i = 0; i < total; ++i) {
-        start_it[i] = pos[i] = solvers[i]->st.mnIterations;
-        mask[i].assign((size_t)std::max(solvers[i]->st.mN1, 1), 0);
-    }
-    // the next success of each listed candidate (s_round = its round, -1: none left)
-    auto refill = [&](const std::vector<int>& list) -> int {
-        if (list.empty()) return RSC_OK;
-        std::vector<rsc_sim3*> act;
-        std::vector<int32_t> its;
-        std::vector<uint8_t*> mp;
-        for (int i : list) {
-            act.push_back(solvers[i]);
-            its.push_back(std::max(1, solvers[i]->st.mRansacMaxIts - solvers[i]->st.mnIterations));
-            mp.push_back(mask[i].data());
-        }
-        std::vector<rsc_sim3_result> r(act.size());
-        if (int st = rsc_sim3_iterate_many(act.data(), (int)act.size(), its.data(), r.data(), mp.data())) return st;
-        for (size_t q = 0; q < list.size(); ++q) {
-            const int i = list[q];
-            per_candidate[i] = r[q];
-            if (!r[q].ok) {
-                s_round[i] = -1;
-                continue;
-            }
-            const int s = r[q].iterations - 1;
-            s_round[i] = calls[i] + (s - pos[i]) / 5;
-            pos[i] = s + 1;
-            calls[i] = s_round[i] + 1;
-        }
-        return RSC_OK;
-    };
-    {
-        std::vector<int> all(total);
-        for (int i = 0; i < total; ++i) all[i] = i;
-        if (int st = refill(all)) return st;
-    }
-    std::vector<char> resolved(n_events, 0);
-    for (;;) {
-        std::vector<int> ev, ci;  // one gate job per unresolved event: its smallest (round, candidate)
-        for (int e = 0; e < n_events; ++e) {
-            if (resolved[e]) continue;
-            int best = -1;
-            for (int i = event_begin[e]; i < event_begin[e + 1]; ++i)
-                if (s_round[i] >= 0 && (best < 0 || s_round[i] < s_round[best])) best = i;
-            if (best < 0) {
-                resolved[e] = 1;  // every candidate discarded: bMatch stays false
-                continue;
-            }
-            ev.push_back(e);
-            ci.push_back(best);
-        }
-        const int J = (int)ev.size();
-        if (J == 0) break;
-        // SearchBySim3 over the RANSAC inliers (vpMapPointMatches[j] = inlier ? match : NULL)
-        std::vector<rsc_kfview*> k1(J), k2(J);
-        std::vector<float> R12(9 * (size_t)J), t12(3 * (size_t)J);
-        std::vector<std::vector<int32_t>> m12(J), o12(J);
-        std::vector<const int32_t*> m12p(J);
-        std::vector<int32_t*> o12p(J);
-        std::vector<int32_t> nfound(J, 0);
-        for (int q = 0; q < J; ++q) {
-            const int i = ci[q];
-            const rsc_loop_candidate& k = cands[i];
-            k1[q] = k.kf1;
-            k2[q] = k.kf2;
-            std::memcpy(&R12[9 * (size_t)q], per_candidate[i].R, 9 * sizeof(float));
-            std::memcpy(&t12[3 * (size_t)q], per_candidate[i].t, 3 * sizeof(float));
-            const int n1 = k.kf1->n;
-            m12[q].assign((size_t)std::max(n1, 1), -1);
-            o12[q].assign((size_t)std::max(n1, 1), -1);
-            for (int a = 0; a < n1; ++a) m12[q][a] = mask[i][a] ? k.matches12[a] : -1;
-            m12p[q] = m12[q].data();
-            o12p[q] = o12[q].data();
-        }
-        if (int st = rsc_search_by_sim3_many(C, k1.data(), k2.data(), J, R12.data(), t12.data(), 7.5f, m12p.data(),
-                                             o12p.data(), nfound.data()))
-            return st;
-        // OptimizeSim3 on vpMapPointMatches after the search (Optimizer.cpp:1108-1171 slot rules)
-        std::vector<rsc_sim3opt_problem> pr(J);
-        std::vector<rsc_sim3opt_result> res(J);
-        std::vector<std::vector<uint8_t>> valid(J), keep(J);
-        std::vector<std::vector<float>> X1(J), X2(J), u1(J), u2(J), i1(J), i2(J);
-        std::vector<uint8_t*> keepp(J);
-        for (int q = 0; q < J; ++q) {
-            const int i = ci[q];
-            const rsc_kfview& a = *cands[i].kf1;
-            const rsc_kfview& b = *cands[i].kf2;
-            const int n1 = a.n;
-            for (int x = 0; x < n1; ++x)
-                if (o12[q][x] >= 0) m12[q][x] = o12[q][x];  // vpMatches12[i1] = vpMapPoints2[idx2]
-            valid[q].assign((size_t)std::max(n1, 1), 0);
-            keep[q].assign((size_t)std::max(n1, 1), 1);
-            X1[q].assign(3 * (size_t)std::max(n1, 1), 0.f);
-            X2[q].assign(3 * (size_t)std::max(n1, 1), 0.f);
-            u1[q].assign(2 * (size_t)std::max(n1, 1), 0.f);
-            u2[q].assign(2 * (size_t)std::max(n1, 1), 0.f);
-            i1[q].assign((size_t)std::max(n1, 1), 0.f);
-            i2[q].assign((size_t)std::max(n1, 1), 0.f);
-            for (int x = 0; x < n1; ++x) {
-                const int y = m12[q][x];
-                // vpMatches1[i] set, pMP1 set, neither bad, i2 = GetIndexInKeyFrame(pKF2) >= 0
-                if (y < 0 || a.mp_state[x] != 1 || b.mp_state[y] != 1) continue;
-                valid[q][x] = 1;
-                for (int c = 0; c < 3; ++c) {
-                    X1[q][3 * x + c] = a.mp_pos[3 * x + c];
-                    X2[q][3 * x + c] = b.mp_pos[3 * (size_t)y + c];
-                }
-                u1[q][2 * x] = a.kp[2 * x];
-                u1[q][2 * x + 1] = a.kp[2 * x + 1];
-                u2[q][2 * x] = b.kp[2 * (size_t)y];
-                u2[q][2 * x + 1] = b.kp[2 * (size_t)y + 1];
-                const int o1 = a.octave[x], o2 = b.octave[y];
-                if (o1 < 0 || o1 >= (int)a.inv_level_sigma2.size() || o2 < 0 || o2 >= (int)b.inv_level_sigma2.size())
-                    return RSC_ERR_ARG;
-                i1[q][x] = a.inv_level_sigma2[o1];
-                i2[q][x] = b.inv_level_sigma2[o2];
-            }
-            rsc_sim3opt_problem& P = pr[q];
-            P.n = n1;
-            P.valid = valid[q].data();
-            P.X1w = X1[q].data();
-            P.X2w = X2[q].data();
-            P.uv1 = u1[q].data();
-            P.uv2 = u2[q].data();
-            P.inv1 = i1[q].data();
-            P.inv2 = i2[q].data();
-            std::memcpy(P.R1w, a.R, sizeof(P.R1w));
-            std::memcpy(P.t1w, a.t, sizeof(P.t1w));
-            std::memcpy(P.R2w, b.R, sizeof(P.R2w));
-            std::memcpy(P.t2w, b.t, sizeof(P.t2w));
-            std::memcpy(P.K1, a.K, sizeof(P.K1));
-            std::memcpy(P.K2, b.K, sizeof(P.K2));
-            // g2o::Sim3 gScm(R.cast<double>(), t.cast<double>(), 1.0): Quaterniond(R), no normalisation
-            double Rd[3][3];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) Rd[r][c] = (double)per_candidate[i].R[3 * r + c];
-            const PoQuat qq = po_quat_from_R(Rd);
-            P.S[0] = qq.x; P.S[1] = qq.y; P.S[2] = qq.z; P.S[3] = qq.w;
-            for (int c = 0; c < 3; ++c) P.S[4 + c] = (double)per_candidate[i].t[c];
-            P.S[7] = 1.0;
-            P.th2 = 10.0f;
-            keepp[q] = keep[q].data();
-        }
-        if (int st = rsc_optimize_sim3_many(C, pr.data(), J, res.data(), keepp.data())) return st;
-        std::vector<int> again;
-        for (int q = 0; q < J; ++q) {
-            const int e = ev[q], i = ci[q];
-            rsc_loop_gate_result& g = per_event[e];
-            if (res[q].n_inliers < 20) {  // LoopClosing.cpp:314: not accepted, the round-robin goes on
-                g.rejected++;
-                again.push_back(i);
-                continue;
-            }
-            g.status = RSC_GATE_MATCH;
-            g.winner = i - event_begin[e];
-            g.round = s_round[i];
-            g.hypothesis = per_candidate[i].iterations - 1 - start_it[i];
-            g.n_inliers = per_candidate[i].n_inliers;
-            g.n_found = nfound[q];
-            g.n_opt_inliers = res[q].n_inliers;
-            std::memcpy(g.S, res[q].S, sizeof(g.S));
-            if (matches_out && matches_out[e]) {
-                const int n1 = cands[i].kf1->n;
-                for (int x = 0; x < n1; ++x) matches_out[e][x] = keep[q][x] ? m12[q][x] : -1;  // outliers NULLed
-            }
-            resolved[e] = 1;
-        }
-        if (int st = refill(again)) return st;
-    }
-    return RSC_OK;
-}
-
 // ---- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and Fuse(pKF, Scw, vpPoints, th, ...) (rsc_kfproj.h) ----
 struct rsc_mpview {
     rsc_context* ctx = nullptr;
@@ -4613,51 +3521,6 @@ int rsc_fuse_sim3_many(rsc_context* C, rsc_kfview* const* kfs, int count, rsc_mp
     return RSC_OK;
 }
 
-// LoopClosing.cpp:318-320 and :360-370 (rsc_sim3compose.h)
-int rsc_loop_verify_many(rsc_context* C, rsc_kfview* const* kf_cur, rsc_kfview* const* kf_matched,
-                         rsc_mpview* const* loop_points, int count, const double* S,
-                         const int32_t* const* matches, const uint8_t* const* already,
-                         rsc_loop_verify_result* res, int32_t* const* projected) {
-    if (!C || count < 0) return RSC_ERR_ARG;
-    if (count == 0) return RSC_OK;
-    if (!kf_cur || !kf_matched || !loop_points || !S || !matches || !already || !res) return RSC_ERR_ARG;
-    std::vector<float> Scw(16 * (size_t)count);
-    std::vector<std::vector<uint8_t>> occ(count);
-    std::vector<std::vector<int32_t>> outs(count);
-    std::vector<const uint8_t*> occp(count);
-    std::vector<int32_t*> outp(count);
-    std::vector<int32_t> nm(count);
-    for (int c = 0; c < count; ++c) {
-        if (!kf_cur[c] || !kf_matched[c] || kf_matched[c]->ctx != C) return RSC_ERR_ARG;
-        const int n = kf_cur[c]->n;
-        if (n && !matches[c]) return RSC_ERR_ARG;
-        const SoSim3 gScm = sc_sim3_from_array(S + 8 * (size_t)c);
-        const SoSim3 gSmw = sc_sim3_from_pose(kf_matched[c]->R, kf_matched[c]->t);  // :318
-        const SoSim3 gScw = sc_compose(gScm, gSmw);                                  // :319
-        sc_sim3_to_array(gScw, res[c].Scw_sim3);
-        sc_to_iso(gScw, res[c].Scw);                                                 // :320
-        std::memcpy(&Scw[16 * (size_t)c], res[c].Scw, sizeof(res[c].Scw));
-        occ[c].assign((size_t)std::max(n, 1), 0);
-        for (int i = 0; i < n; ++i) occ[c][i] = matches[c][i] != -1;  // -2 is a non-null pointer
-        outs[c].assign((size_t)std::max(n, 1), -1);
-        occp[c] = occ[c].data();
-        outp[c] = outs[c].data();
-    }
-    if (int st = rsc_search_by_projection_kf_many(C, kf_cur, loop_points, count, Scw.data(), already, occp.data(),
-                                                  10, outp.data(), nm.data(), nullptr))  // :360
-        return st;
-    for (int c = 0; c < count; ++c) {
-        const int n = kf_cur[c]->n;
-        int total = nm[c];
-        for (int i = 0; i < n; ++i) total += occ[c][i];  // :363-368
-        res[c].n_projected = nm[c];
-        res[c].n_total = total;
-        res[c].accepted = total >= 40;  // :370
-        if (projected && projected[c] && n) std::memcpy(projected[c], outs[c].data(), 4 * (size_t)n);
-    }
-    return RSC_OK;
-}
-
 // ---- Tracking::SearchLocalPoints: isInFrustum + SearchByProjection(Frame&, vector<MapPoint>&, th) (rsc_localproj.h) ----
 namespace {
 static_assert(sizeof(rsc_track_record) == sizeof(LpTrack), "rsc_track_record layout");
@@ -4793,17 +3656,6 @@ int rsc_search_by_projection_points_many(rsc_context* C, rsc_frameview* const* f
 }
 
 // ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th) (ORBmatcher.cpp:1173-1315, rsc_lastproj.h) ----
-struct rsc_lastframe {
-    rsc_context* ctx = nullptr;
-    int n = 0;
-    DevBuf<char> mem;  // octave | angle | mp_state | mp_pos | mp_desc | mp_has_obs
-    DevLastFrame dev;  // device pointers
-    // host copies: the argument check and the motion-model driver read them
-    std::vector<int32_t> octave;
-    std::vector<uint8_t> mp_state, mp_has_obs;
-    std::vector<float> mp_pos;
-};
-
 int rsc_lastframe_create(rsc_context* C, const rsc_last_frame_slots* s, rsc_lastframe** out) {
     if (!C || !s || !out) return RSC_ERR_ARG;
     *out = nullptr;
@@ -4849,7 +3701,6 @@ void rsc_lastframe_destroy(rsc_lastframe* v) {
     delete v;
 }
 
-namespace {
 // what rsc_search_by_projection_last_many refuses before any launch
 int last_check_args(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts, int count, float th) {
     // GetFeaturesInArea converts (u - mnMinX + r) * mfGridElementWidthInv to int, undefined out of int's
@@ -4883,7 +3734,6 @@ int last_check_args(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe*
     }
     return 0;
 }
-}  // namespace
 
 int rsc_search_by_projection_last_many(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts,
                                        int count, const float* Tcw_cur, const float* Tcw_last, const float* mb,
@@ -4958,131 +3808,4 @@ int rsc_search_by_projection_last_many(rsc_context* C, rsc_frameview* const* fra
     return RSC_OK;
 }
 
-// Tracking::TrackWithMotionModel (Tracking.cpp:724-774); each stage one launch over the frames still in it.
-int rsc_track_motion_model_many(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts, int count,
-                                const float* Tcw_cur, const float* Tcw_last, const float* mb, float th,
-                                const int32_t* only_tracking, rsc_track_motion_result* result, int32_t* const* out,
-                                int32_t* const* discarded) {
-    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
-    if (count == 0) return RSC_OK;
-    if (!frames || !lasts || !Tcw_cur || !Tcw_last || !mb || !only_tracking || !result || !out || !discarded)
-        return RSC_ERR_ARG;
-    if (int e = last_check_args(C, frames, lasts, count, th)) return e;
-    if (int e = last_check_args(C, frames, lasts, count, 2.0f * th)) return e;
-    for (int c = 0; c < count; ++c)
-        if (frames[c]->n && (!out[c] || !discarded[c])) return RSC_ERR_ARG;
-    std::vector<int32_t> nm(count), md(count);
-    // :724-732: from an empty mvpMapPoints (frame_occ NULL)
-    if (int st = rsc_search_by_projection_last_many(C, frames, lasts, count, Tcw_cur, Tcw_last, mb, nullptr, th, 1,
-                                                    out, nm.data(), md.data(), nullptr))
-        return st;
-    std::vector<int> again, opt;
-    for (int c = 0; c < count; ++c) {
-        rsc_track_motion_result& r = result[c];
-        std::memset(&r, 0, sizeof(r));
-        r.searches = 1;
-        r.nmatches_search[0] = nm[c];
-        r.nmatches_search[1] = -1;
-        r.mode = md[c];
-        r.nmatches = nm[c];
-        std::memcpy(r.Tcw, Tcw_cur + 16 * (size_t)c, sizeof(r.Tcw));
-        for (int f = 0; f < frames[c]->n; ++f) discarded[c][f] = -1;
-        if (nm[c] < 20) again.push_back(c);  // :735
-    }
-    if (!again.empty()) {  // :737-738: again from empty, at 2 * th
-        const int m = (int)again.size();
-        std::vector<rsc_frameview*> F(m);
-        std::vector<rsc_lastframe*> L(m);
-        std::vector<float> Tc(16 * (size_t)m), Tl(16 * (size_t)m), b(m);
-        std::vector<int32_t*> op(m);
-        std::vector<int32_t> nm2(m);
-        for (int q = 0; q < m; ++q) {
-            const int c = again[q];
-            F[q] = frames[c];
-            L[q] = lasts[c];
-            std::memcpy(&Tc[16 * (size_t)q], Tcw_cur + 16 * (size_t)c, 16 * sizeof(float));
-            std::memcpy(&Tl[16 * (size_t)q], Tcw_last + 16 * (size_t)c, 16 * sizeof(float));
-            b[q] = mb[c];
-            op[q] = out[c];
-        }
-        if (int st = rsc_search_by_projection_last_many(C, F.data(), L.data(), m, Tc.data(), Tl.data(), b.data(),
-                                                        nullptr, 2.0f * th, 1, op.data(), nm2.data(), nullptr, nullptr))
-            return st;
-        for (int q = 0; q < m; ++q) {
-            rsc_track_motion_result& r = result[again[q]];
-            r.searches = 2;
-            r.nmatches_search[1] = nm2[q];
-            r.nmatches = nm2[q];
-        }
-    }
-    for (int c = 0; c < count; ++c) {
-        for (int f = 0; f < frames[c]->n; ++f)
-            if (out[c][f] < 0) out[c][f] = -1;  // a slot the rotation check nulled is empty
-        if (result[c].nmatches >= 20) opt.push_back(c);  // :741
-    }
-    if (opt.empty()) return RSC_OK;
-    // :745 Optimizer::PoseOptimization(&mCurrentFrame) on every occupied slot
-    const int m = (int)opt.size();
-    std::vector<std::vector<uint8_t>> has(m), outl(m);
-    std::vector<std::vector<float>> Xw(m), inv(m);
-    std::vector<rsc_poseopt_problem> pr(m);
-    std::vector<rsc_poseopt_result> res(m);
-    std::vector<uint8_t*> olp(m);
-    for (int q = 0; q < m; ++q) {
-        const int c = opt[q];
-        const rsc_frameview& F = *frames[c];
-        const rsc_lastframe& L = *lasts[c];
-        const size_t n = (size_t)F.n;
-        has[q].assign(std::max(n, (size_t)1), 0);
-        outl[q].assign(std::max(n, (size_t)1), 0);
-        Xw[q].assign(3 * std::max(n, (size_t)1), 0.f);
-        inv[q].assign(std::max(n, (size_t)1), 0.f);
-        for (size_t f = 0; f < n; ++f) {
-            const int32_t s = out[c][f];
-            if (s < 0) continue;
-            has[q][f] = 1;
-            for (int k = 0; k < 3; ++k) Xw[q][3 * f + k] = L.mp_pos[3 * (size_t)s + k];
-            inv[q][f] = F.inv_level_sigma2[F.octave[f]];
-        }
-        rsc_poseopt_problem& P = pr[q];
-        P.n = F.n;
-        P.has_mp = has[q].data();
-        P.uv = F.kp.data();
-        P.Xw = Xw[q].data();
-        P.inv_sigma2 = inv[q].data();
-        P.u_right = F.h_uright.data();
-        P.fx = F.K[0]; P.fy = F.K[1]; P.cx = F.K[2]; P.cy = F.K[3];
-        std::memcpy(P.Tcw, result[c].Tcw, sizeof(P.Tcw));
-        P.bf = F.mbf;
-        olp[q] = outl[q].data();
-    }
-    if (int st = rsc_pose_optimization_many(C, pr.data(), m, res.data(), olp.data())) return st;
-    for (int q = 0; q < m; ++q) {
-        const int c = opt[q];
-        const rsc_lastframe& L = *lasts[c];
-        rsc_track_motion_result& r = result[c];
-        r.n_good = res[q].n_good;
-        std::memcpy(r.Tcw, res[q].Tcw, sizeof(r.Tcw));
-        int map = 0;
-        for (int f = 0; f < frames[c]->n; ++f) {  // :749-766
-            const int32_t s = out[c][f];
-            if (s < 0) continue;
-            if (outl[q][f]) {
-                discarded[c][f] = s;
-                out[c][f] = -1;
-                r.nmatches--;
-            } else if (L.mp_has_obs[s]) {
-                ++map;
-            }
-        }
-        r.nmatches_map = map;
-        if (only_tracking[c]) {  // :768-772
-            r.vo = map < 10;
-            r.ok = r.nmatches > 20;
-        } else {
-            r.ok = map >= 10;  // :774
-        }
-    }
-    return RSC_OK;
-}
 }  // extern "C"
