@@ -937,6 +937,72 @@ int rsc_voc_last_kernel_timing(rsc_voc* voc, double* ms2);
 int rsc_bow_create_transformed(rsc_context* ctx, rsc_voc* voc, const rsc_bow_features* features, int levelsup,
                                rsc_bow** out, rsc_voc_output* bow);
 
+/* ---- LocalMapping::CreateNewMapPoints: SearchForTriangulation and the triangulation ------------
+ * What triangulation reads and a rsc_kfview lacks (in the style of rsc_kfview_set_angles). */
+typedef struct {
+    const float* u_right;              /* [n] mvuRight (negative: monocular; `>= 0` is stereo, ORBmatcher.cpp:537) */
+    const float* depth;                /* [n] mvDepth */
+    const float* kp_raw;               /* [n][2] mvKeys[i].pt: UnprojectStereo reads mvKeys, not mvKeysUn
+                                          (KeyFrame.cpp:611-612) */
+    const float* cos_parallax_stereo;  /* [n] cos(2*atan2(mb/2, mvDepth[i])), the expression of
+                                          LocalMapping.cpp:286,288 evaluated by the caller's libm; read only
+                                          where u_right[i] >= 0 */
+    float mb, mbf, invfx, invfy;
+    float scale_factor;                /* mfScaleFactor */
+    float Rwc[9], Ow[3];               /* Twc as KeyFrame::SetPose stored it (KeyFrame.cpp:64-66), row-major */
+    float Kinv[9];                     /* KeyFrame::mKinv, row-major (ComputeF12, LocalMapping.cpp:527-528) */
+} rsc_kf_triangulation;
+int rsc_kfview_set_triangulation(rsc_kfview* view, const rsc_kf_triangulation* t);
+
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cpp:489-669)
+ * for c < count in one launch.  bow1[c] / kf1[c] are the two resident views of KeyFrame 1 (same n), bow2[c] /
+ * kf2[c] of KeyFrame 2; both kfviews carry rsc_kfview_set_triangulation.  F12: [count][9] row-major.
+ * has_mp1 / has_mp2 (the arrays or single entries may be NULL): uint8 [n], GetMapPoint(idx) != nullptr, bad
+ * points included; NULL takes the view's mp_state != 0.  only_stereo: [count] bOnlyStereo of each call (NULL: all
+ * false).  check_orientation: mbCheckOrientation (a member of the matcher object in the reference, so one value
+ * per launch), read from the rsc_bow views' angles.  Outputs: matches12[c][i1] = KeyFrame-2 index or -1 (vMatchedPairs = its non-negative
+ * entries in ascending i1), nmatches[c], den_zero[c] = 1 when an eligible slot's epipolar line had den == 0
+ * (`return false`, :552-553: nmatches 0, all -1, the reference leaves vMatchedPairs untouched), den_zero_slot
+ * [c][i1] = 1 on those slots (either may be NULL).  vbMatched2 is never set in the reference, so two slots may
+ * share a KeyFrame-2 feature; reproduced.  RSC_ERR_ARG before any launch: n > 8192, bow / kfview sizes that
+ * differ, a view without rsc_kfview_set_triangulation, a KeyFrame-2 octave outside [0, n_levels), a
+ * non-finite F12. */
+int rsc_search_for_triangulation_many(rsc_context* ctx, const rsc_bow* const* bow1, rsc_kfview* const* kf1,
+                                      const rsc_bow* const* bow2, rsc_kfview* const* kf2, int count,
+                                      const float* F12, const uint8_t* const* has_mp1,
+                                      const uint8_t* const* has_mp2, const int32_t* only_stereo,
+                                      int check_orientation,
+                                      int32_t* const* matches12, int32_t* nmatches, int32_t* den_zero,
+                                      uint8_t* const* den_zero_slot);
+
+/* The body of CreateNewMapPoints' match loop (LocalMapping.cpp:262-407) for npairs[c] pairs (idx1 in kf1[c] =
+ * the current KeyFrame, idx2 in kf2[c]), pairs[c]: int32 [npairs][2].  status[c][k] names the `continue` the
+ * pair took: 0 success, 1 temp(3) == 0 (:309), 2 no stereo and low parallax (:326), 3 z1 <= 0, 4 z2 <= 0,
+ * 5 / 6 reprojection error in KeyFrame 1 / 2, 7 a zero distance (:398), 8 scale consistency (:406); x3d[c][k]
+ * [3] the point.  The float JacobiSVD<Matrix4f> is restated (two-sided Jacobi; parity with an Eigen build
+ * unpinned).  Quirks kept: cosParallaxStereo2 is read only when KeyFrame 1's feature is not stereo (:287);
+ * KeyFrame 2's right-image error uses the current KeyFrame's mbf (:382).  RSC_ERR_ARG: an index or octave
+ * out of range, a view without rsc_kfview_set_triangulation. */
+int rsc_triangulate_pairs_many(rsc_context* ctx, rsc_kfview* const* kf1, rsc_kfview* const* kf2, int count,
+                               const int32_t* npairs, const int32_t* const* pairs, int32_t* const* status,
+                               float* const* x3d);
+
+/* LocalMapping::CreateNewMapPoints' neighbour loop (LocalMapping.cpp:224-428) for count current KeyFrames:
+ * neighbours neigh_begin[c] .. neigh_begin[c + 1] of bow_neigh / kf_neigh are vpNeighKFs of c in order (pass
+ * only as many as the caller is prepared to process: CheckNewKeyFrames, :226, cannot be polled inside the
+ * call).  Per neighbour: the baseline gate (:232-236), ComputeF12 (:512-531) on the host,
+ * SearchForTriangulation(.., false) with the orientation check off (ORBmatcher matcher(0.6, false), :202),
+ * the triangulation; a success fills the KeyFrame-1 slot, which later neighbours skip.  One matcher launch
+ * and one triangulation launch from the initial slot state (mp_state != 0), then the neighbour order is
+ * replayed on the host.  Outputs per current KeyFrame, indexed by its slot i1 (a slot is filled at most
+ * once): new_neighbour[c][i1] = index into c's neighbour list or -1, new_idx2[c][i1], new_pos[c][i1][3],
+ * nnew[c].  The reference's creation order is (neighbour, i1) ascending.  MapPoint allocation,
+ * AddObservation / AddMapPoint, ComputeDistinctiveDescriptors and UpdateNormalAndDepth stay with the caller. */
+int rsc_create_new_map_points_many(rsc_context* ctx, const rsc_bow* const* bow_cur, rsc_kfview* const* kf_cur,
+                                   int count, const int32_t* neigh_begin, const rsc_bow* const* bow_neigh,
+                                   rsc_kfview* const* kf_neigh, int32_t* const* new_neighbour,
+                                   int32_t* const* new_idx2, float* const* new_pos, int32_t* nnew);
+
 /* Diagnostics below: `cap` = number of uint64 slots at `out`; RSC_ERR_ARG when it is smaller than
  * the layout (64*24, 64*8, 4096*4 and at most 64*96 words).
  * Diagnostic: wall-clock (100 MHz) phase stamps of the last PnP refine launch, [job < 64][24]:

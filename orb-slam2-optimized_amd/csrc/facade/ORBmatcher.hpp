@@ -43,11 +43,18 @@
 // Observations(), and of the current Frame additionally mb; the helper also needs mnId, mvbOutlier, mTcw(r, c)
 // and SetPose as rsc_orb::PoseOptimization does, and writes mbTrackInView / mnLastFrameSeen on the MapPoints it
 // discards as outliers.
+//
+// SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cpp:489-669;
+// LocalMapping.cpp:242) reads the KeyFrames as SearchBySim3 does plus mFeatVec, mvKeys[i].pt, mvuRight, mvDepth,
+// mb, mbf, invfx, invfy, mfScaleFactor, mKinv and the stored inverse pose, the one protected member, through the
+// customization point kf_pose_inverse (default: the reference's public KeyFrame::GetPoseInverse()).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <set>
 #include <stdexcept>
+#include <utility>
 #include <vector>
 #include "rsc_context.hpp"
 
@@ -200,6 +207,47 @@ KFViewUpload upload_kfview(const KFPtr& pKF, const std::vector<MPPtr>& mps) {
     u.n = n;
     check(rsc_kfview_create(thread_context(), &k, &u.h), "rsc_kfview_create");
     return u;
+}
+
+// Customization point: Twc as KeyFrame::SetPose stored it (KeyFrame.cpp:64-66), an object with rotation() /
+// translation() (Eigen::Isometry3f).
+template <class KF>
+auto kf_pose_inverse(KF& kf) { return kf.GetPoseInverse(); }
+
+// What triangulation reads and the view lacks (rsc_kfview_set_triangulation).  cos_parallax_stereo is the
+// expression of LocalMapping.cpp:286,288 on this host's libm.
+template <class KFPtr>
+void set_triangulation(KFViewUpload& u, const KFPtr& pKF) {
+    using std::atan2;
+    using std::cos;
+    auto& K = *pKF;
+    const size_t n = (size_t)u.n;
+    std::vector<float> ur(n), depth(n), raw(2 * n), cs(n);
+    for (size_t i = 0; i < n; ++i) {
+        ur[i] = K.mvuRight[i];
+        depth[i] = K.mvDepth[i];
+        raw[2 * i] = K.mvKeys[i].pt.x;
+        raw[2 * i + 1] = K.mvKeys[i].pt.y;
+        cs[i] = cos(2*atan2(K.mb/2,K.mvDepth[i]));
+    }
+    rsc_kf_triangulation t;
+    t.u_right = ur.data();
+    t.depth = depth.data();
+    t.kp_raw = raw.data();
+    t.cos_parallax_stereo = cs.data();
+    t.mb = K.mb; t.mbf = K.mbf; t.invfx = K.invfx; t.invfy = K.invfy;
+    t.scale_factor = K.mfScaleFactor;
+    const auto Twc = kf_pose_inverse(K);
+    const auto R = Twc.rotation();
+    const auto O = Twc.translation();
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            t.Rwc[3 * r + c] = R(r, c);
+            t.Kinv[3 * r + c] = K.mKinv(r, c);
+        }
+        t.Ow[r] = O(r);
+    }
+    check(rsc_kfview_set_triangulation(u.h, &t), "rsc_kfview_set_triangulation");
 }
 
 // The current Frame's SearchByProjection inputs uploaded to HBM (rsc_frameview_create).
@@ -515,6 +563,40 @@ public:
                 if (out[c][i] >= 0) m[i] = mp2[out[c][i]];
         }
         return std::vector<int>(nfound.begin(), nfound.begin() + C);
+    }
+
+    // SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cpp:489-669;
+    // LocalMapping.cpp:242): the matches of KeyFrame 1's features without a MapPoint against KeyFrame 2's under the
+    // epipolar constraint, in ascending idx1.  When an eligible feature's epipolar line has den == 0 the
+    // reference returns 0 before it touches vMatchedPairs (:552-553); so does this.
+    template <class KFPtr, class Mat3>
+    int SearchForTriangulation(KFPtr pKF1, KFPtr pKF2, const Mat3& F12,
+                               std::vector<std::pair<size_t, size_t>>& vMatchedPairs, const bool bOnlyStereo) {
+        detail::BowUpload b1 = detail::upload_keyframe(pKF1), b2 = detail::upload_keyframe(pKF2);
+        detail::KFViewUpload v1 = detail::upload_kfview(pKF1, pKF1->GetMapPointMatches());
+        detail::KFViewUpload v2 = detail::upload_kfview(pKF2, pKF2->GetMapPointMatches());
+        detail::set_triangulation(v1, pKF1);
+        detail::set_triangulation(v2, pKF2);
+        float F[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) F[3 * r + c] = F12(r, c);
+        std::vector<int32_t> m12((size_t)(v1.n > 0 ? v1.n : 1), -1);
+        int32_t* out = m12.data();
+        int32_t nmatches = 0, den_zero = 0;
+        const rsc_bow* pb1 = b1.h;
+        const rsc_bow* pb2 = b2.h;
+        const int32_t only_stereo = bOnlyStereo ? 1 : 0;
+        // the views' mp_state is GetMapPoint(idx) != nullptr, bad points included: no per-call flags
+        check(rsc_search_for_triangulation_many(thread_context(), &pb1, &v1.h, &pb2, &v2.h, 1, F, nullptr, nullptr,
+                                                &only_stereo, mbCheckOrientation ? 1 : 0, &out, &nmatches, &den_zero,
+                                                nullptr),
+              "SearchForTriangulation");
+        if (den_zero) return 0;  // `return false`: vMatchedPairs untouched
+        vMatchedPairs.clear();
+        vMatchedPairs.reserve((size_t)nmatches);
+        for (int i = 0; i < v1.n; ++i)
+            if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));
+        return nmatches;
     }
 
     // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1317-1444): the

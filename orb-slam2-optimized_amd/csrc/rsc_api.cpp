@@ -3808,4 +3808,246 @@ int rsc_search_by_projection_last_many(rsc_context* C, rsc_frameview* const* fra
     return RSC_OK;
 }
 
+// ---- LocalMapping::CreateNewMapPoints: SearchForTriangulation and the triangulation (rsc_triang.h) ----
+int rsc_kfview_set_triangulation(rsc_kfview* v, const rsc_kf_triangulation* t) {
+    if (!v || !t) return RSC_ERR_ARG;
+    const size_t n = (size_t)std::max(v->n, 0);
+    if (n && (!t->u_right || !t->depth || !t->kp_raw || !t->cos_parallax_stereo)) return RSC_ERR_ARG;
+    RSC_HIP(hipSetDevice(v->ctx->device));
+    const size_t o_raw = 0, o_ur = al256(8 * n), o_dp = o_ur + al256(4 * n), o_cs = o_dp + al256(4 * n);
+    const size_t bytes = o_cs + al256(4 * n);
+    if (int e = v->tri_mem.ensure(std::max(bytes, (size_t)256))) return e;
+    std::vector<char> h(std::max(bytes, (size_t)256), 0);
+    if (n) {
+        std::memcpy(h.data() + o_raw, t->kp_raw, 8 * n);
+        std::memcpy(h.data() + o_ur, t->u_right, 4 * n);
+        std::memcpy(h.data() + o_dp, t->depth, 4 * n);
+        std::memcpy(h.data() + o_cs, t->cos_parallax_stereo, 4 * n);
+    }
+    RSC_HIP(hipStreamSynchronize(v->ctx->stream));
+    RSC_HIP(hipMemcpy(v->tri_mem.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    char* d = v->tri_mem.p;
+    TriView& K = v->tri;
+    K.kp = reinterpret_cast<const float*>(v->dev.kp);
+    K.kp_raw = reinterpret_cast<const float*>(d + o_raw);
+    K.octave = v->dev.octave;
+    K.scale = v->dev.scale;
+    K.u_right = reinterpret_cast<const float*>(d + o_ur);
+    K.depth = reinterpret_cast<const float*>(d + o_dp);
+    K.cos_stereo = reinterpret_cast<const float*>(d + o_cs);
+    std::memcpy(K.Rcw, v->R, sizeof(K.Rcw));
+    std::memcpy(K.tcw, v->t, sizeof(K.tcw));
+    std::memcpy(K.Rwc, t->Rwc, sizeof(K.Rwc));
+    std::memcpy(K.Ow, t->Ow, sizeof(K.Ow));
+    K.fx = v->K[0]; K.fy = v->K[1]; K.cx = v->K[2]; K.cy = v->K[3];
+    K.invfx = t->invfx; K.invfy = t->invfy; K.mb = t->mb; K.mbf = t->mbf;
+    K.scale_factor = t->scale_factor;
+    K.n = v->n;
+    K.n_levels = v->dev.n_levels;
+    v->n_levels = v->dev.n_levels;
+    v->h_uright.assign(t->u_right, t->u_right + n);
+    std::memcpy(v->Kinv, t->Kinv, sizeof(v->Kinv));
+    v->has_triang = true;
+    return RSC_OK;
+}
+
+namespace {
+int tri_check_view(const rsc_context* C, const rsc_kfview* k) {
+    if (!k || k->ctx != C) return RSC_ERR_ARG;
+    if (k->n > kTriMaxFeatures) {
+        g_last_error = "more than 8192 keypoints in one view";
+        return RSC_ERR_ARG;
+    }
+    if (!k->has_triang) {
+        g_last_error = "a KeyFrame view without rsc_kfview_set_triangulation";
+        return RSC_ERR_ARG;
+    }
+    return 0;
+}
+}  // namespace
+
+int rsc_search_for_triangulation_many(rsc_context* C, const rsc_bow* const* bow1, rsc_kfview* const* kf1,
+                                      const rsc_bow* const* bow2, rsc_kfview* const* kf2, int count,
+                                      const float* F12, const uint8_t* const* has_mp1,
+                                      const uint8_t* const* has_mp2, const int32_t* only_stereo,
+                                      int check_orientation, int32_t* const* matches12, int32_t* nmatches,
+                                      int32_t* den_zero, uint8_t* const* den_zero_slot) {
+    return tri_search_impl(C, bow1, kf1, bow2, kf2, count, F12, has_mp1, has_mp2, only_stereo, check_orientation,
+                           /*speculative=*/0, matches12, nmatches, den_zero, den_zero_slot);
+}
+
+// speculative (rsc_create_new_map_points_many, orientation off): a problem with den_zero keeps its matches12
+int tri_search_impl(rsc_context* C, const rsc_bow* const* bow1, rsc_kfview* const* kf1, const rsc_bow* const* bow2,
+                    rsc_kfview* const* kf2, int count, const float* F12, const uint8_t* const* has_mp1,
+                    const uint8_t* const* has_mp2, const int32_t* only_stereo, int check_orientation, int speculative,
+                    int32_t* const* matches12, int32_t* nmatches, int32_t* den_zero, uint8_t* const* den_zero_slot) {
+    if (!C || count < 0 || (speculative && check_orientation)) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!bow1 || !kf1 || !bow2 || !kf2 || !F12 || !matches12) return RSC_ERR_ARG;
+    for (int c = 0; c < count; ++c) {
+        if (int e = tri_check_view(C, kf1[c])) return e;
+        if (int e = tri_check_view(C, kf2[c])) return e;
+        if (!bow1[c] || !bow2[c] || bow1[c]->ctx != C || bow2[c]->ctx != C) return RSC_ERR_ARG;
+        if (bow1[c]->n != kf1[c]->n || bow2[c]->n != kf2[c]->n) {
+            g_last_error = "the rsc_bow and the rsc_kfview of one KeyFrame differ in size";
+            return RSC_ERR_ARG;
+        }
+        if (kf1[c]->n && !matches12[c]) return RSC_ERR_ARG;
+        for (int i = 0; i < 9; ++i)
+            if (!std::isfinite(F12[9 * (size_t)c + i])) {
+                g_last_error = "non-finite F12";
+                return RSC_ERR_ARG;
+            }
+        const rsc_kfview& k2 = *kf2[c];
+        for (int i = 0; i < k2.n; ++i)
+            if (k2.octave[i] < 0 || k2.octave[i] >= k2.n_levels) {
+                g_last_error = "KeyFrame-2 keypoint octave out of range";
+                return RSC_ERR_ARG;
+            }
+    }
+    // layout: problem table | has1 | has2  (uploaded)  | items | item counts | node table  (scratch)  |
+    // matches12 | den_zero_slot | counts  (the part that comes back)
+    std::vector<size_t> o_h1(count), o_h2(count), o_it(count), o_ni(count), o_m(count), o_dz(count), o_cnt(count);
+    Arena A;
+    A.take(sizeof(TriMatchProblem) * count);
+    for (int c = 0; c < count; ++c) {
+        o_h1[c] = A.take((size_t)std::max(kf1[c]->n, 1));
+        o_h2[c] = A.take((size_t)std::max(kf2[c]->n, 1));
+    }
+    A.end_upload();
+    for (int c = 0; c < count; ++c) {
+        o_it[c] = A.take(sizeof(int4) * kTriClasses * (size_t)std::max(bow1[c]->n_feat, 1));
+        o_ni[c] = A.take(16);
+    }
+    const size_t o_nodes = A.take(sizeof(int2) * (size_t)kTriMaxFeatures * count);
+    A.end_scratch();
+    for (int c = 0; c < count; ++c) {
+        o_m[c] = A.take(4 * (size_t)std::max(kf1[c]->n, 1));
+        o_dz[c] = A.take((size_t)std::max(kf1[c]->n, 1));
+        o_cnt[c] = A.take(8);
+    }
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const rsc_kfview& k1 = *kf1[c];
+            const rsc_kfview& k2 = *kf2[c];
+            const uint8_t* g1 = has_mp1 ? has_mp1[c] : nullptr;
+            const uint8_t* g2 = has_mp2 ? has_mp2[c] : nullptr;
+            uint8_t* a1 = reinterpret_cast<uint8_t*>(h + o_h1[c]);
+            uint8_t* a2 = reinterpret_cast<uint8_t*>(h + o_h2[c]);
+            const bool stereo_only = only_stereo && only_stereo[c] != 0;
+            // a skipped feature: it has a MapPoint (:534, :567), or bOnlyStereo and it is not stereo (:539-541,
+            // :572-574; `>= 0`, false for a NaN)
+            for (int i = 0; i < k1.n; ++i)
+                a1[i] = (g1 ? (g1[i] != 0) : (k1.mp_state[i] != 0)) || (stereo_only && !(k1.h_uright[i] >= 0));
+            for (int i = 0; i < k2.n; ++i)
+                a2[i] = (g2 ? (g2[i] != 0) : (k2.mp_state[i] != 0)) || (stereo_only && !(k2.h_uright[i] >= 0));
+            TriMatchProblem p;
+            p.A = bow1[c]->hdr;
+            p.B = bow2[c]->hdr;
+            p.kp1 = k1.dev.kp;
+            p.kp2 = k2.dev.kp;
+            p.oct2 = k2.dev.octave;
+            p.scale2 = k2.dev.scale;
+            p.ur1 = k1.tri.u_right;
+            p.ur2 = k2.tri.u_right;
+            p.angle1 = bow1[c]->hdr.angle;
+            p.angle2 = bow2[c]->hdr.angle;
+            p.has1 = reinterpret_cast<const uint8_t*>(d + o_h1[c]);
+            p.has2 = reinterpret_cast<const uint8_t*>(d + o_h2[c]);
+            std::memcpy(p.F, F12 + 9 * (size_t)c, sizeof(p.F));
+            // the epipole (:496-502): Cw = pKF1->GetCameraCenter() = Ow
+            tri_epipole(k2.R, k2.t, k1.tri.Ow, k2.K[0], k2.K[1], k2.K[2], k2.K[3], p.ex, p.ey);
+            p.items = reinterpret_cast<int4*>(d + o_it[c]);
+            p.nitems = reinterpret_cast<int32_t*>(d + o_ni[c]);
+            p.matches12 = reinterpret_cast<int32_t*>(d + o_m[c]);
+            p.den_zero_slot = reinterpret_cast<uint8_t*>(d + o_dz[c]);
+            p.counts = reinterpret_cast<int32_t*>(d + o_cnt[c]);
+            std::memcpy(h + sizeof(TriMatchProblem) * c, &p, sizeof(p));
+        }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_search_for_triangulation(count, reinterpret_cast<const TriMatchProblem*>(d),
+                                               reinterpret_cast<int2*>(d + o_nodes),
+                                               (check_orientation ? 1 : 0) | (speculative ? 2 : 0), C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch)) return e;
+    const char* h = C->h_fp.p;
+    for (int c = 0; c < count; ++c) {
+        const size_t n1 = (size_t)kf1[c]->n;
+        if (n1) std::memcpy(matches12[c], h + o_m[c], 4 * n1);
+        if (n1 && den_zero_slot && den_zero_slot[c]) std::memcpy(den_zero_slot[c], h + o_dz[c], n1);
+        if (nmatches) std::memcpy(&nmatches[c], h + o_cnt[c], 4);
+        if (den_zero) std::memcpy(&den_zero[c], h + o_cnt[c] + 4, 4);
+    }
+    return RSC_OK;
+}
+
+int rsc_triangulate_pairs_many(rsc_context* C, rsc_kfview* const* kf1, rsc_kfview* const* kf2, int count,
+                               const int32_t* npairs, const int32_t* const* pairs, int32_t* const* status,
+                               float* const* x3d) {
+    if (!C || count < 0) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!kf1 || !kf2 || !npairs || !pairs || !status || !x3d) return RSC_ERR_ARG;
+    int max_pairs = 0;
+    for (int c = 0; c < count; ++c) {
+        if (int e = tri_check_view(C, kf1[c])) return e;
+        if (int e = tri_check_view(C, kf2[c])) return e;
+        if (npairs[c] < 0 || (npairs[c] && (!pairs[c] || !status[c] || !x3d[c]))) return RSC_ERR_ARG;
+        const rsc_kfview& k1 = *kf1[c];
+        const rsc_kfview& k2 = *kf2[c];
+        for (int i = 0; i < npairs[c]; ++i) {
+            const int32_t i1 = pairs[c][2 * i], i2 = pairs[c][2 * i + 1];
+            if (i1 < 0 || i1 >= k1.n || i2 < 0 || i2 >= k2.n) {
+                g_last_error = "pair index out of range";
+                return RSC_ERR_ARG;
+            }
+            if (k1.octave[i1] < 0 || k1.octave[i1] >= k1.n_levels || k2.octave[i2] < 0 ||
+                k2.octave[i2] >= k2.n_levels) {
+                g_last_error = "keypoint octave out of range";
+                return RSC_ERR_ARG;
+            }
+        }
+        max_pairs = std::max(max_pairs, npairs[c]);
+    }
+    // layout: problem table | pairs  (uploaded)  |  status | x3d  (the part that comes back)
+    std::vector<size_t> o_p(count), o_st(count), o_x(count);
+    Arena A;
+    A.take(sizeof(TriPairsProblem) * count);
+    for (int c = 0; c < count; ++c) o_p[c] = A.take(8 * (size_t)std::max(npairs[c], 1));
+    A.end_upload();
+    A.end_scratch();
+    for (int c = 0; c < count; ++c) {
+        o_st[c] = A.take(4 * (size_t)std::max(npairs[c], 1));
+        o_x[c] = A.take(12 * (size_t)std::max(npairs[c], 1));
+    }
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            if (npairs[c]) std::memcpy(h + o_p[c], pairs[c], 8 * (size_t)npairs[c]);
+            TriPairsProblem p;
+            p.K1 = kf1[c]->tri;
+            p.K2 = kf2[c]->tri;
+            p.pairs = reinterpret_cast<const int32_t*>(d + o_p[c]);
+            p.npairs = npairs[c];
+            p.status = reinterpret_cast<int32_t*>(d + o_st[c]);
+            p.x3d = reinterpret_cast<float*>(d + o_x[c]);
+            std::memcpy(h + sizeof(TriPairsProblem) * c, &p, sizeof(p));
+        }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_triangulate_pairs(count, max_pairs, reinterpret_cast<const TriPairsProblem*>(d), C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch)) return e;
+    const char* h = C->h_fp.p;
+    for (int c = 0; c < count; ++c) {
+        if (!npairs[c]) continue;
+        std::memcpy(status[c], h + o_st[c], 4 * (size_t)npairs[c]);
+        std::memcpy(x3d[c], h + o_x[c], 12 * (size_t)npairs[c]);
+    }
+    return RSC_OK;
+}
+
 }  // extern "C"

@@ -767,4 +767,133 @@ int rsc_track_motion_model_many(rsc_context* C, rsc_frameview* const* frames, rs
     }
     return RSC_OK;
 }
+
+// LocalMapping::CreateNewMapPoints' neighbour loop (LocalMapping.cpp:224-428), speculated on the device and
+// replayed on the host (the shape of the RANSAC engine).
+//
+// Why the replay is exact.  The loop over neighbours is sequential only through the current KeyFrame's slots: a
+// successful triangulation fills slot idx1 (:415) and the next neighbour's matcher skips a filled slot before
+// anything else (ORBmatcher.cpp:531-535).  Inside one SearchForTriangulation call a slot is decided alone:
+// vbMatched2 is never set (read at :567, written nowhere), and with the orientation check off (ORBmatcher
+// matcher(0.6, false), :202) no histogram couples the slots.  So the match, the den == 0 flag and the
+// triangulation of (neighbour i, slot s) computed from the INITIAL slot state are the ones the reference
+// computes whenever it reaches s with the slot still empty, and are never looked at otherwise.  The neighbour's
+// own slots change only after its matcher returned (:416), and a covisibility list names a KeyFrame once.  The
+// replay walks the neighbours in order: a neighbour is void when one of its den == 0 slots is still empty
+// (`return false` leaves vMatchedIndices empty); otherwise every match on a still-empty slot whose
+// triangulation succeeded is emitted in ascending idx1 and fills the slot.  The problems of one call are each
+// evaluated from the views' state at the call.
+int rsc_create_new_map_points_many(rsc_context* C, const rsc_bow* const* bow_cur, rsc_kfview* const* kf_cur, int count,
+                                   const int32_t* neigh_begin, const rsc_bow* const* bow_neigh,
+                                   rsc_kfview* const* kf_neigh, int32_t* const* new_neighbour,
+                                   int32_t* const* new_idx2, float* const* new_pos, int32_t* nnew) {
+    if (!C || count < 0) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!bow_cur || !kf_cur || !neigh_begin || !new_neighbour || !new_idx2 || !new_pos || !nnew) return RSC_ERR_ARG;
+    if (neigh_begin[0] != 0) return RSC_ERR_ARG;
+    for (int c = 0; c < count; ++c)
+        if (neigh_begin[c + 1] < neigh_begin[c]) return RSC_ERR_ARG;
+    const int total = neigh_begin[count];
+    if (total && (!bow_neigh || !kf_neigh)) return RSC_ERR_ARG;
+    auto usable = [&](const rsc_kfview* k) {
+        if (!k || k->ctx != C) return false;
+        if (!k->has_triang) g_last_error = "a KeyFrame view without rsc_kfview_set_triangulation";
+        return k->has_triang;
+    };
+    for (int c = 0; c < count; ++c) {
+        if (!usable(kf_cur[c]) || !bow_cur[c]) return RSC_ERR_ARG;
+        if (kf_cur[c]->n && (!new_neighbour[c] || !new_idx2[c] || !new_pos[c])) return RSC_ERR_ARG;
+    }
+    for (int g = 0; g < total; ++g)
+        if (!usable(kf_neigh[g]) || !bow_neigh[g]) return RSC_ERR_ARG;
+    // the baseline gate (:232-236) and ComputeF12 (:512-531) on the host
+    std::vector<int> sel_c, sel_g;
+    std::vector<float> F;
+    for (int c = 0; c < count; ++c)
+        for (int g = neigh_begin[c]; g < neigh_begin[c + 1]; ++g) {
+            const rsc_kfview& k1 = *kf_cur[c];
+            const rsc_kfview& k2 = *kf_neigh[g];
+            if (tri_baseline_short(k1.tri.Ow, k2.tri.Ow, k2.tri.mb)) continue;
+            float f[9];
+            tri_compute_f12(k1.R, k1.t, k2.tri.Rwc, k2.tri.Ow, k1.Kinv, k2.Kinv, f);
+            F.insert(F.end(), f, f + 9);
+            sel_c.push_back(c);
+            sel_g.push_back(g);
+        }
+    const int J = (int)sel_c.size();
+    std::vector<std::vector<int32_t>> m((size_t)J), pairs((size_t)J), status((size_t)J);
+    std::vector<std::vector<uint8_t>> dzs((size_t)J);
+    std::vector<std::vector<float>> x3d((size_t)J);
+    if (J) {
+        // one matcher launch over every (problem, neighbour) that passed the gate, from the initial slots
+        std::vector<const rsc_bow*> b1(J), b2(J);
+        std::vector<rsc_kfview*> k1(J), k2(J);
+        std::vector<int32_t*> mp(J);
+        std::vector<uint8_t*> dp(J);
+        for (int j = 0; j < J; ++j) {
+            b1[j] = bow_cur[sel_c[j]];
+            k1[j] = kf_cur[sel_c[j]];
+            b2[j] = bow_neigh[sel_g[j]];
+            k2[j] = kf_neigh[sel_g[j]];
+            const size_t n1 = (size_t)std::max(k1[j]->n, 1);
+            m[j].assign(n1, -1);
+            dzs[j].assign(n1, 0);
+            mp[j] = m[j].data();
+            dp[j] = dzs[j].data();
+        }
+        if (int st = tri_search_impl(C, b1.data(), k1.data(), b2.data(), k2.data(), J, F.data(), nullptr, nullptr,
+                                     /*only_stereo=*/nullptr, /*check_orientation=*/0, /*speculative=*/1, mp.data(), nullptr,
+                                     nullptr, dp.data()))
+            return st;
+        // one triangulation launch over all matches
+        std::vector<int32_t> np(J);
+        std::vector<const int32_t*> pp(J);
+        std::vector<int32_t*> sp(J);
+        std::vector<float*> xp(J);
+        for (int j = 0; j < J; ++j) {
+            for (int i = 0; i < k1[j]->n; ++i)
+                if (m[j][i] >= 0) {
+                    pairs[j].push_back(i);
+                    pairs[j].push_back(m[j][i]);
+                }
+            np[j] = (int32_t)(pairs[j].size() / 2);
+            status[j].assign((size_t)std::max(np[j], 1), -1);
+            x3d[j].assign(3 * (size_t)std::max(np[j], 1), 0.0f);
+            pp[j] = pairs[j].data();
+            sp[j] = status[j].data();
+            xp[j] = x3d[j].data();
+        }
+        if (int st = rsc_triangulate_pairs_many(C, k1.data(), k2.data(), J, np.data(), pp.data(), sp.data(), xp.data()))
+            return st;
+    }
+    // the replay: neighbours in order, slots filled as the reference fills them
+    int j = 0;
+    for (int c = 0; c < count; ++c) {
+        const rsc_kfview& k1 = *kf_cur[c];
+        std::vector<uint8_t> filled(k1.mp_state.size());
+        for (size_t i = 0; i < filled.size(); ++i) filled[i] = k1.mp_state[i] != 0;
+        for (int i = 0; i < k1.n; ++i) {
+            new_neighbour[c][i] = -1;
+            new_idx2[c][i] = -1;
+            new_pos[c][3 * i] = new_pos[c][3 * i + 1] = new_pos[c][3 * i + 2] = 0.0f;
+        }
+        nnew[c] = 0;
+        for (; j < J && sel_c[j] == c; ++j) {
+            bool voided = false;
+            for (int i = 0; i < k1.n && !voided; ++i) voided = dzs[j][i] && !filled[i];
+            if (voided) continue;
+            const int np = (int)(pairs[j].size() / 2);
+            for (int k = 0; k < np; ++k) {
+                const int i1 = pairs[j][2 * k];
+                if (filled[i1] || status[j][k] != 0) continue;
+                new_neighbour[c][i1] = sel_g[j] - neigh_begin[c];
+                new_idx2[c][i1] = pairs[j][2 * k + 1];
+                std::memcpy(new_pos[c] + 3 * i1, x3d[j].data() + 3 * k, 12);
+                filled[i1] = 1;
+                ++nnew[c];
+            }
+        }
+    }
+    return RSC_OK;
+}
 }  // extern "C"

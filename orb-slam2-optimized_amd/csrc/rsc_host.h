@@ -10,6 +10,7 @@
 #include "rsc_sim3match.h"
 #include "rsc_frameproj.h"
 #include "rsc_lastproj.h"
+#include "rsc_triang.h"
 
 using namespace rsc;
 #pragma GCC visibility push(hidden)  // what this block declares stays out of the library's exported symbols
@@ -234,6 +235,14 @@ struct rsc_kfview {
     DevSim3KF dev;           // the header as uploaded (device pointers), for SearchByProjection's problem table
     DevBuf<float> d_angle;   // mvKeysUn[i].angle (rsc_kfview_set_angles)
     bool has_angles = false;
+    // rsc_kfview_set_triangulation: kp_raw | u_right | depth | cos_stereo on the device, the view as the pair
+    // geometry reads it (device pointers), and the host copies the drivers and the argument checks read
+    DevBuf<char> tri_mem;
+    TriView tri;
+    std::vector<float> h_uright;
+    float Kinv[9];
+    int n_levels = 0;
+    bool has_triang = false;
 };
 
 struct rsc_frameview {
@@ -266,3 +275,13 @@ struct rsc_lastframe {
 // what rsc_search_by_projection_last_many refuses before any launch (an exported name since it exists)
 extern "C" int last_check_args(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts, int count,
                                float th);
+
+#pragma GCC visibility push(hidden)
+// rsc_search_for_triangulation_many with the driver's switch (not an exported symbol): speculative = 1 leaves the
+// matches of a problem with den_zero in place (rsc_create_new_map_points_many's replay reads them when every
+// den == 0 slot has been filled by an earlier neighbour)
+extern "C" int tri_search_impl(rsc_context* C, const rsc_bow* const* bow1, rsc_kfview* const* kf1, const rsc_bow* const* bow2,
+                    rsc_kfview* const* kf2, int count, const float* F12, const uint8_t* const* has_mp1,
+                    const uint8_t* const* has_mp2, const int32_t* only_stereo, int check_orientation, int speculative,
+                    int32_t* const* matches12, int32_t* nmatches, int32_t* den_zero, uint8_t* const* den_zero_slot);
+#pragma GCC visibility pop

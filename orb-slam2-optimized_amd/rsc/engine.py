@@ -62,6 +62,8 @@ EXPORTED = [
     "rsc_frameview_set_stereo", "rsc_search_local_points_many", "rsc_search_by_projection_points_many",
     "rsc_lastframe_create", "rsc_lastframe_destroy", "rsc_search_by_projection_last_many",
     "rsc_track_motion_model_many",
+    "rsc_kfview_set_triangulation", "rsc_search_for_triangulation_many", "rsc_triangulate_pairs_many",
+    "rsc_create_new_map_points_many",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -188,6 +190,14 @@ class Sim3KFStruct(C.Structure):
                 ("mp_dmax", C.c_void_p), ("mp_dmin", C.c_void_p), ("mp_desc", C.c_void_p)]
 
 
+class KFTriangulation(C.Structure):
+    """rsc_kf_triangulation (include/rsc.h)."""
+    _fields_ = [("u_right", C.c_void_p), ("depth", C.c_void_p), ("kp_raw", C.c_void_p),
+                ("cos_parallax_stereo", C.c_void_p), ("mb", C.c_float), ("mbf", C.c_float), ("invfx", C.c_float),
+                ("invfy", C.c_float), ("scale_factor", C.c_float), ("Rwc", C.c_float * 9), ("Ow", C.c_float * 3),
+                ("Kinv", C.c_float * 9)]
+
+
 def sim3_kf_struct(kf):
     """(ctypes rsc_sim3_kf, keep-alive arrays) for a rsc.synth.Sim3KF-like object."""
     from rsc import synth
@@ -231,6 +241,22 @@ class KFView:
             raise ValueError(f"{self.n} angles expected, got {a.size}")
         _check(load_library().rsc_kfview_set_angles(self.h, a if a.size else np.zeros(1, np.float32)),
                "rsc_kfview_set_angles")
+
+    def set_triangulation(self, tri):
+        """What CreateNewMapPoints reads and the view lacks (rsc_kfview_set_triangulation): an object with u_right,
+        depth, cos_parallax_stereo float32 [n], kp_raw float32 [n,2], mb, mbf, invfx, invfy, scale_factor, Rwc [3,3],
+        Ow [3] (Twc as KeyFrame::SetPose stores it) and Kinv [3,3] (KeyFrame::mKinv)."""
+        pad = lambda a, k: (np.ascontiguousarray(a, np.float32).reshape(-1) if self.n else np.zeros(k, np.float32))
+        keep = [pad(tri.u_right, 1), pad(tri.depth, 1), pad(tri.kp_raw, 2), pad(tri.cos_parallax_stereo, 1)]
+        assert keep[0].size == max(self.n, 1) and keep[2].size == 2 * max(self.n, 1)
+        t = KFTriangulation()
+        t.u_right, t.depth, t.kp_raw, t.cos_parallax_stereo = (a.ctypes.data for a in keep)
+        t.mb, t.mbf, t.invfx, t.invfy = float(tri.mb), float(tri.mbf), float(tri.invfx), float(tri.invfy)
+        t.scale_factor = float(tri.scale_factor)
+        t.Rwc[:] = [float(v) for v in np.asarray(tri.Rwc, np.float32).reshape(9)]
+        t.Ow[:] = [float(v) for v in np.asarray(tri.Ow, np.float32).reshape(3)]
+        t.Kinv[:] = [float(v) for v in np.asarray(tri.Kinv, np.float32).reshape(9)]
+        _check(load_library().rsc_kfview_set_triangulation(self.h, C.byref(t)), "rsc_kfview_set_triangulation")
 
     def close(self):
         if getattr(self, "h", None):
@@ -506,6 +532,74 @@ def track_motion_model_many(ctx: Context, frames, lasts, Tcw_cur, Tcw_last, mb, 
         ot, res, _ptrs(out), _ptrs(disc)), "rsc_track_motion_model_many")
     return (np.ctypeslib.as_array(res).copy()[:c], [o[:f.n] for o, f in zip(out, frames)],
             [d[:f.n] for d, f in zip(disc, frames)])
+
+
+def _opt_flags(flags, views):
+    """Per-call uint8 [n] flag arrays (entries may be None) as a pointer table, or None for the whole argument."""
+    if flags is None:
+        return None, []
+    keep = [None if a is None else (np.ascontiguousarray(a, np.uint8) if v.n else np.zeros(1, np.uint8))
+            for a, v in zip(flags, views)]
+    return (C.c_void_p * max(len(keep), 1))(*[None if a is None else a.ctypes.data for a in keep]), keep
+
+
+def search_for_triangulation_many(ctx: Context, bow1, kf1, bow2, kf2, F12, has_mp1=None, has_mp2=None,
+                                  only_stereo: bool = False, check_orientation: bool = False):
+    """ORBmatcher::SearchForTriangulation (ORBmatcher.cpp:489-669) for each (BowView, KFView of KeyFrame 1, BowView,
+    KFView of KeyFrame 2, F12 [3,3]) in one launch; the KFViews carry set_triangulation.  has_mp1 / has_mp2: lists
+    of uint8 [n] (GetMapPoint(idx) != nullptr) or None = the views' mp_state != 0; only_stereo: one bool or one per
+    problem.  Returns a dict: matches12 (list
+    of int32 [n1]: KeyFrame-2 index or -1), nmatches, den_zero (int32 [count]), den_zero_slot (list of uint8 [n1])."""
+    c = len(kf1)
+    F = np.ascontiguousarray(np.asarray(F12, np.float32).reshape(c, 9)) if c else np.zeros((1, 9), np.float32)
+    out = [np.full(max(k.n, 1), -7, np.int32) for k in kf1]
+    dzs = [np.full(max(k.n, 1), 7, np.uint8) for k in kf1]
+    nm, dz = (np.full(max(c, 1), -7, np.int32) for _ in range(2))
+    os_ = np.zeros(max(c, 1), np.int32)
+    os_[:c] = np.asarray(only_stereo, np.int32)  # one value, or one per problem
+    h1, keep1 = _opt_flags(has_mp1, kf1)
+    h2, keep2 = _opt_flags(has_mp2, kf2)
+    _check(load_library().rsc_search_for_triangulation_many(
+        ctx.h, _handles(bow1), _handles(kf1), _handles(bow2), _handles(kf2), c, F, h1, h2, os_,
+        int(check_orientation), _ptrs(out), nm, dz, _ptrs(dzs)), "rsc_search_for_triangulation_many")
+    return dict(matches12=[o[:k.n] for o, k in zip(out, kf1)], nmatches=nm[:c], den_zero=dz[:c],
+                den_zero_slot=[d[:k.n] for d, k in zip(dzs, kf1)])
+
+
+def triangulate_pairs_many(ctx: Context, kf1, kf2, pairs):
+    """The pair geometry of LocalMapping::CreateNewMapPoints (LocalMapping.cpp:262-407) for each (KFView of the
+    current KeyFrame, KFView of the neighbour, pairs int32 [np,2]).  Returns (list of status int32 [np], list of
+    x3d float32 [np,3])."""
+    c = len(kf1)
+    pr = [np.ascontiguousarray(p, np.int32).reshape(-1, 2) for p in pairs]
+    npairs = np.array([len(p) for p in pr] or [0], np.int32)
+    pr = [p if len(p) else np.zeros((1, 2), np.int32) for p in pr]
+    st = [np.full(max(int(n), 1), -7, np.int32) for n in npairs[:c]]
+    x = [np.full((max(int(n), 1), 3), np.nan, np.float32) for n in npairs[:c]]
+    _check(load_library().rsc_triangulate_pairs_many(ctx.h, _handles(kf1), _handles(kf2), c, npairs, _ptrs(pr),
+                                                      _ptrs(st), _ptrs(x)), "rsc_triangulate_pairs_many")
+    return [s[:n] for s, n in zip(st, npairs)], [a[:n] for a, n in zip(x, npairs)]
+
+
+def create_new_map_points_many(ctx: Context, bow_cur, kf_cur, bow_neigh, kf_neigh):
+    """LocalMapping::CreateNewMapPoints' neighbour loop (LocalMapping.cpp:224-428, rsc_create_new_map_points_many)
+    for each current KeyFrame (BowView, KFView) with its ordered neighbour lists bow_neigh[c] / kf_neigh[c].
+    Returns a dict of per-KeyFrame lists: new_neighbour int32 [n] (-1 = none), new_idx2 int32 [n], new_pos float32
+    [n,3], and nnew int32 [count]."""
+    c = len(kf_cur)
+    begin = np.zeros(c + 1, np.int32)
+    begin[1:] = np.cumsum([len(k) for k in kf_neigh])
+    fb = [b for bs in bow_neigh for b in bs]
+    fk = [k for ks in kf_neigh for k in ks]
+    nn = [np.full(max(k.n, 1), -7, np.int32) for k in kf_cur]
+    i2 = [np.full(max(k.n, 1), -7, np.int32) for k in kf_cur]
+    pos = [np.full((max(k.n, 1), 3), np.nan, np.float32) for k in kf_cur]
+    nnew = np.full(max(c, 1), -7, np.int32)
+    _check(load_library().rsc_create_new_map_points_many(ctx.h, _handles(bow_cur), _handles(kf_cur), c, begin,
+                                                          _handles(fb), _handles(fk), _ptrs(nn), _ptrs(i2), _ptrs(pos),
+                                                          nnew), "rsc_create_new_map_points_many")
+    return dict(new_neighbour=[a[:k.n] for a, k in zip(nn, kf_cur)], new_idx2=[a[:k.n] for a, k in zip(i2, kf_cur)],
+                new_pos=[a[:k.n] for a, k in zip(pos, kf_cur)], nnew=nnew[:c])
 
 
 def fuse_sim3_many(ctx: Context, kfs, points, Scw, in_kf, th: float):
@@ -890,6 +984,14 @@ def load_library(path: str = LIB_PATH):
     L.rsc_track_motion_model_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, f32p_, f32p_, f32p_,
                                               C.c_float, i32p, C.POINTER(TrackMotionResult),
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rsc_kfview_set_triangulation.argtypes = [vp, C.POINTER(KFTriangulation)]
+    L.rsc_search_for_triangulation_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                    C.c_int, f32p_, C.POINTER(vp), C.POINTER(vp), i32p, C.c_int,
+                                                    C.POINTER(vp), i32p, i32p, C.POINTER(vp)]
+    L.rsc_triangulate_pairs_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, i32p, C.POINTER(vp),
+                                             C.POINTER(vp), C.POINTER(vp)]
+    L.rsc_create_new_map_points_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, i32p, C.POINTER(vp),
+                                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32p]
     L.rsc_voc_create.argtypes = [vp, C.POINTER(VocabularyNodes), C.POINTER(vp)]
     L.rsc_voc_destroy.argtypes = [vp]
     L.rsc_voc_destroy.restype = None
