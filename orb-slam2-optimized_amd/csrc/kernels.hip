@@ -156,14 +156,19 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
                                                        int32_t* __restrict__ counts_dev,
                                                        uint64_t* __restrict__ masks, int mask_words,
                                                        int32_t* __restrict__ qual) {
-    // Hypotheses per flush: the 4 waves' mask words of a batch wait in LDS (16 KB) until the batch's
-    // counts are summed; only hypotheses reaching mRansacMinInliers — the only ones whose inlier
-    // mask the host ever adopts (PnPsolver.cpp:176-195) — are stored.  In exhaustive
-    // relocalization batches almost none qualify, so the 4.8 MB of mask writes per config-2
-    // launch become a few KB.
+    // Hypotheses per flush: the 4 waves' counts of a batch wait in LDS until the batch's totals are
+    // summed.  The only inlier mask of a round's problem that is ever read is the one of its FIRST
+    // hypothesis reaching mRansacMinInliers: the replay pauses there (rsc_engine.h
+    // pnp_iterate_many: pause_k, adopted if it beats the best), pnp_select_refine_kernel selects the
+    // same one, the Refine reads it, and after the Refine the solver is done or the rest of the
+    // round is speculated again (PnPsolver.cpp:176-195).  So the loop keeps no mask words: the
+    // flushes note the chunk's first qualifying hypothesis — the problem's first is the first of
+    // its chunk — and its ballots are taken a second time after the chunk is counted (ballots()
+    // below, the same code on the same pose record) and stored.  In exhaustive relocalization
+    // batches none qualifies, and the loop pays nothing for the masks.
     constexpr int B = PPT <= 8 ? 64 : 512 / PPT;
     __shared__ int wave_cnt[4][B];
-    __shared__ uint64_t mbuf[B][4][PPT];
+    __shared__ int first_sh;  // the chunk's first qualifying hypothesis, -1: none (set by every flush)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int4 wt = wg_table[blockIdx.x];
     const LaunchProb& lp = lps[wt.x];
@@ -209,24 +214,10 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
         const int hj = w / 12, k = w - 12 * hj;
         poses[(rec0 + hj) * 12 + k] = pose_of(hj)[k];
     }
-    // The PPT points of a lane are independent: all ballots are taken first and the mask words
-    // are kept by lanes 0..PPT-1 in one predicated store, so the compiler can interleave the
-    // points' arithmetic (a lane-0 branch per point would serialise them).  The next pose is
-    // loaded before the current one is used.
-    const float* pp = pose_of(0);
-    float Rn[9], tn[3];
-    RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
-    RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
-    for (int j = 0; j < wt.z; ++j) {
-        float R[9], t[3];
-        RSC_UNROLL for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-        RSC_UNROLL for (int k = 0; k < 3; ++k) t[k] = tn[k];
-        if (j + 1 < wt.z) {
-            pp = pose_of(j + 1);
-            RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
-            RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
-        }
-        uint64_t b[PPT];
+    // The wave's PPT inlier words of one pose.  The PPT points of a lane are independent: all
+    // ballots are taken before anything is done with them, so the compiler can interleave the
+    // points' arithmetic.  The counting pass and the mask pass both go through here.
+    auto ballots = [&](const float (&R)[9], const float (&t)[3], uint64_t (&b)[PPT]) {
         if constexpr (PPT >= 2) {
             bool ok = true;
             RSC_UNROLL for (int s = 0; s < PPT; s += 2) {
@@ -247,36 +238,70 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
             RSC_UNROLL for (int s = 0; s < PPT; ++s)
                 b[s] = __ballot(pnp_inlier(R, t, fx, fy, cx, cy, X[s], Y[s], Z[s], U[s], V[s], E[s]));
         }
-        int cnt = 0;
-        uint64_t mine = 0;
-        RSC_UNROLL for (int s = 0; s < PPT; ++s) {
-            cnt += __popcll(b[s]);
-            mine = (lane == s) ? b[s] : mine;
+    };
+    // Two passes through ONE loop body (a second copy of ballots() in the kernel costs registers:
+    // 104 VGPRs instead of at most 96 at PPT 8, a workgroup per CU less).  Pass 0 takes every
+    // hypothesis of the chunk and counts; pass 1 takes the chunk's first qualifying one again and
+    // stores its mask words.  `todo` holds the pass' hypotheses as bits (scalar); the next pose is
+    // loaded before the current one is used.
+    uint64_t todo = wt.z >= 64 ? ~0ull : (1ull << wt.z) - 1;
+    int first = -1;  // wave 0: the chunk's first qualifying hypothesis so far
+    for (int pass = 0; pass < 2; ++pass) {
+        float Rn[9] = {}, tn[3] = {};
+        if (todo) {
+            const float* pp = pose_of(__ffsll((unsigned long long)todo) - 1);
+            RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
+            RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
         }
-        const int jb = j % B;
-        if (lane < PPT) mbuf[jb][wave][lane] = mine;
-        if (lane == 0) wave_cnt[wave][jb] = cnt;
-        if (jb == B - 1 || j == wt.z - 1) {
-            __syncthreads();
-            const int base = j - jb;
-            if (tid <= jb) {
-                const int c = wave_cnt[0][tid] + wave_cnt[1][tid] + wave_cnt[2][tid] + wave_cnt[3][tid];
-                counts[lp.out0 + wt.y + base + tid] = c;
-                if (counts_dev) counts_dev[lp.out0 + wt.y + base + tid] = c;  // pnp_select_refine_kernel
-                // the problem has a hypothesis reaching mRansacMinInliers: the host replay reads its
-                // counts (it skips the counts of a problem without one, rsc_engine.h)
-                if (c >= lp.min_inliers) qual[wt.x] = 1;
-                wave_cnt[0][tid] = c;  // the batch's totals, for the mask stores below
+        while (todo) {
+            const int j = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            float R[9], t[3];
+            RSC_UNROLL for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+            RSC_UNROLL for (int k = 0; k < 3; ++k) t[k] = tn[k];
+            if (todo) {
+                const float* pp = pose_of(__ffsll((unsigned long long)todo) - 1);
+                RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
+                RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
             }
-            __syncthreads();
-            if (masks) {
-                for (int w = tid; w < (jb + 1) * 4 * PPT; w += 256) {
-                    const int hb = w / (4 * PPT), r = w - hb * (4 * PPT), s = r >> 2, wv = r & 3;
-                    if (wave_cnt[0][hb] >= lp.min_inliers)
-                        masks[(size_t)(lp.out0 + wt.y + base + hb) * mask_words + r] = mbuf[hb][wv][s];
+            uint64_t b[PPT];
+            ballots(R, t, b);
+            if (pass == 1) {
+                // word 4 s + wave of the hypothesis' mask row = points 256 s + 64 wave + lane
+                if (lane == 0) {
+                    uint64_t* row = masks + (rec0 + (size_t)j) * mask_words;
+                    RSC_UNROLL for (int s = 0; s < PPT; ++s) row[4 * s + wave] = b[s];
                 }
+                continue;
             }
-            __syncthreads();
+            int cnt = 0;
+            RSC_UNROLL for (int s = 0; s < PPT; ++s) cnt += __popcll(b[s]);
+            const int jb = j % B;
+            if (lane == 0) wave_cnt[wave][jb] = cnt;
+            if (jb == B - 1 || !todo) {
+                __syncthreads();
+                const int base = j - jb;
+                bool q = false;
+                if (tid <= jb) {
+                    const int c = wave_cnt[0][tid] + wave_cnt[1][tid] + wave_cnt[2][tid] + wave_cnt[3][tid];
+                    counts[lp.out0 + wt.y + base + tid] = c;
+                    if (counts_dev) counts_dev[lp.out0 + wt.y + base + tid] = c;  // pnp_select_refine_kernel
+                    // the problem has a hypothesis reaching mRansacMinInliers: the host replay reads its
+                    // counts (it skips the counts of a problem without one, rsc_engine.h)
+                    q = c >= lp.min_inliers;
+                    if (q) qual[wt.x] = 1;
+                }
+                // jb < B <= 64: the batch's totals are all in wave 0, whose ballot is the batch's
+                // qualifiers (the other waves see none and do not write)
+                const uint64_t qb = __ballot(q);
+                if (first < 0 && qb) first = base + __ffsll((unsigned long long)qb) - 1;
+                if (tid == 0) first_sh = first;
+                __syncthreads();  // the totals are read (the next batch overwrites wave_cnt); first_sh is set
+            }
+        }
+        if (pass == 0 && masks && wt.z > 0) {
+            const int f = __builtin_amdgcn_readfirstlane(first_sh);
+            if (f >= 0) todo = 1ull << f;
         }
     }
 }

@@ -96,9 +96,9 @@ bool scan_wgs_overridden() {
 
 // Scan workgroups of a PnP round: chunks[i] even chunks for problem i's H[i] hypotheses (sizes
 // differ by at most one, even_chunk below).  `capacity` is what the device holds at once
-// (pnp_scan_kernel<PPT>'s workgroups per CU x CUs) and `batch` the kernel's mask batch B.
+// (pnp_scan_kernel<PPT>'s workgroups per CU x CUs) and `batch` the kernel's batch B (hypotheses per flush).
 //   * The round gets k x capacity workgroups, dealt to the problems in proportion to their
-//     hypotheses, with the smallest k whose chunks fit one mask batch: whole rounds of residency, so
+//     hypotheses, with the smallest k whose chunks fit one batch: whole rounds of residency, so
 //     no CU idles through a part-filled last round, and each workgroup's head (table -> launch
 //     record -> problem -> points) is paid for as many hypotheses as a full device allows
 //     (config 2: 1,280 x 15 instead of 2,432 x 8 or 4).
@@ -514,6 +514,8 @@ struct HipPnPBackend : PnPBackend {
             if (int e = C->d_selout.ensure((size_t)count)) return e;
             if (int e = C->h_selout.ensure((size_t)count)) return e;
         }
+        // of a round's mask rows only the one of each scan chunk's first qualifying hypothesis is
+        // written (pnp_scan_kernel, pass 1); every other row holds what earlier rounds left
         if (int e = C->d_masks.ensure((size_t)total * mw)) return e;
         if (int e = C->d_samples.ensure((size_t)total * 8)) return e;
         if (int e = C->d_stage.ensure((size_t)total * kStageDoubles)) return e;
