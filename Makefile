@@ -11,7 +11,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
-     facade_lastproj_test facade_triang_test arena_test rounds_test triang_emu
+     facade_lastproj_test facade_triang_test arena_test rounds_test triang_emu fusekf_emu facade_fusekf_test
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -37,7 +37,7 @@ $(LIBDIR)/librsc_spin1.so: $(OBJS:%/kernels.o=%/kernels_spin1.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 FACADE_TESTS = facade_test facade_proj_test facade_loopproj_test facade_localproj_test facade_lastproj_test \
-               facade_triang_test facade_voc_test
+               facade_triang_test facade_fusekf_test facade_voc_test
 
 $(FACADE_TESTS): %: $(LIBDIR)/%
 
@@ -108,9 +108,12 @@ lastproj_emu:
 triang_emu:
 	$(MAKE) -s -C tests/triang_emu
 
+fusekf_emu:
+	$(MAKE) -s -C tests/fusekf_emu
+
 clean:
 	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
-	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build
+	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build
 
-.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
+.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
         facade_voc_test chase_mirror_test arena_test rounds_test clean

@@ -1003,6 +1003,24 @@ int rsc_create_new_map_points_many(rsc_context* ctx, const rsc_bow* const* bow_c
                                    rsc_kfview* const* kf_neigh, int32_t* const* new_neighbour,
                                    int32_t* const* new_idx2, float* const* new_pos, int32_t* nnew);
 
+/* ---- LocalMapping::SearchInNeighbors: ORBmatcher::Fuse(pKF, vpMapPoints, th) -------------------------
+ * Fuse(pKF = kfs[c], vpMapPoints = points[c], th) (src/ORBmatcher.cpp:671-821) for c < count in one launch
+ * over every (point, KeyFrame) pair: the matcher of :698-795.  points[c] may be one view repeated (the forward
+ * loop of LocalMapping.cpp:461-466) or a view per problem; the points need not be distinct, no pair depends on
+ * another.  The pose is the view's Rcw / tcw, the camera centre its rsc_kf_triangulation.Ow (the stored
+ * Twc.translation()), mvuRight / mbf come from there too, and mvInvLevelSigma2[l] is derived as
+ * 1.0f / (scale_factors[l] * scale_factors[l]).  A keypoint with u_right >= 0 (zero included) is stereo: chi2
+ * 7.8 over (ex, ey, er), else 5.99 over (ex, ey).  skip[c][i] (points[c] n entries): isBad() ||
+ * IsInKeyFrame(pKF) at launch; a view state of 2 skips as well.  best_idx[c][i]: bestIdx when bestDist <= 50,
+ * else -1; nfused[c] (may be NULL): the number of best_idx[c][i] >= 0.  The bookkeeping of :797-817 (Replace,
+ * AddObservation, AddMapPoint) mutates the caller's map and stays with the caller, in list order
+ * (facade/ORBmatcher.hpp replays it).  RSC_ERR_ARG before any launch: a kfview without
+ * rsc_kfview_set_triangulation, n > 8192, a keypoint octave outside [0, n_levels), a non-finite th, th *
+ * scale[n_levels - 1] * grid_inv >= 2^30 (the bound of rsc_search_by_sim3_many).  count == 0 and empty point
+ * lists are RSC_OK. */
+int rsc_fuse_kf_many(rsc_context* ctx, rsc_kfview* const* kfs, rsc_mpview* const* points, int count,
+                     const uint8_t* const* skip, float th, int32_t* const* best_idx, int32_t* nfused);
+
 /* Diagnostics below: `cap` = number of uint64 slots at `out`; RSC_ERR_ARG when it is smaller than
  * the layout (64*24, 64*8, 4096*4 and at most 64*96 words).
  * Diagnostic: wall-clock (100 MHz) phase stamps of the last PnP refine launch, [job < 64][24]:

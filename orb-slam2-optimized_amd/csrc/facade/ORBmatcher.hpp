@@ -347,6 +347,62 @@ LastFrameUpload upload_lastframe(const FrameT& L) {
     return u;
 }
 
+// A MapPoint list on the device (rsc_mpview_create) and its host arrays, for Fuse(pKF, vpMapPoints, th): the
+// descriptor bytes are kept because a Replace can change a survivor's descriptor between two KeyFrames.
+struct MPViewUpload {
+    rsc_mpview* h = nullptr;
+    MPViewUpload() = default;
+    MPViewUpload(const MPViewUpload&) = delete;
+    MPViewUpload& operator=(const MPViewUpload&) = delete;
+    MPViewUpload(MPViewUpload&& o) noexcept : h(o.h) { o.h = nullptr; }
+    ~MPViewUpload() { rsc_mpview_destroy(h); }
+};
+
+struct FusePoints {
+    std::vector<uint8_t> state, desc;
+    std::vector<float> pos, nrm, dmax, dmin;
+    explicit FusePoints(size_t n)
+        : state(n > 0 ? n : 1, 2), desc(32 * (n > 0 ? n : 1), 0), pos(3 * (n > 0 ? n : 1), 0.f),
+          nrm(3 * (n > 0 ? n : 1), 0.f), dmax(n > 0 ? n : 1, 0.f), dmin(n > 0 ? n : 1, 0.f) {}
+    template <class MP>
+    void set(size_t i, MP& mp) {
+        if (mp.isBad()) return;  // state 2
+        state[i] = 1;
+        const auto X = mp.GetWorldPos();
+        const auto N = mp.GetNormal();
+        for (int c = 0; c < 3; ++c) {
+            pos[3 * i + c] = X(c);
+            nrm[3 * i + c] = N(c);
+        }
+        dmax[i] = mp_max_distance(mp);
+        dmin[i] = mp_min_distance(mp);
+        const auto d = mp.GetDescriptor();
+        const uint8_t* dr = d.template ptr<uint8_t>(0);
+        std::copy(dr, dr + 32, desc.begin() + 32 * i);
+    }
+    void copy(size_t i, const FusePoints& o, size_t j) {
+        state[i] = o.state[j];
+        std::copy(o.pos.begin() + 3 * j, o.pos.begin() + 3 * j + 3, pos.begin() + 3 * i);
+        std::copy(o.nrm.begin() + 3 * j, o.nrm.begin() + 3 * j + 3, nrm.begin() + 3 * i);
+        dmax[i] = o.dmax[j];
+        dmin[i] = o.dmin[j];
+        std::copy(o.desc.begin() + 32 * j, o.desc.begin() + 32 * j + 32, desc.begin() + 32 * i);
+    }
+    MPViewUpload upload(size_t n) const {
+        rsc_mappoints m;
+        m.n = (int32_t)n;
+        m.state = state.data();
+        m.pos = pos.data();
+        m.normal = nrm.data();
+        m.dmax = dmax.data();
+        m.dmin = dmin.data();
+        m.desc = desc.data();
+        MPViewUpload u;
+        check(rsc_mpview_create(thread_context(), &m, &u.h), "rsc_mpview_create");
+        return u;
+    }
+};
+
 template <class IsoT>
 void iso_to_array16(const IsoT& S, float* T) {
     const auto R = S.rotation();
@@ -840,6 +896,130 @@ public:
         return std::vector<int>(nf.begin(), nf.begin() + C);
     }
 
+    // Fuse(pKF, vpMapPoints, th) (ORBmatcher.cpp:671-821; LocalMapping.cpp:465 and :490).  vpMapPoints may hold
+    // null and repeated pointers (GetMapPointMatches() has both kinds).  KeyFrame additionally needs
+    // mvInvLevelSigma2, GetMapPoint(idx), AddMapPoint(pMP, idx) and what set_triangulation reads; MapPoint
+    // IsInKeyFrame(pKF), Observations(), Replace(pMP), AddObservation(pKF, idx) and GetNormal().
+    template <class KFPtr, class MPPtr>
+    int Fuse(KFPtr pKF, const std::vector<MPPtr>& vpMapPoints, float th = 3.0f) {
+        std::vector<KFPtr> k(1, pKF);
+        return FuseMany(k, vpMapPoints, th)[0];
+    }
+
+    // The loop of LocalMapping::SearchInNeighbors over its target KeyFrames (LocalMapping.cpp:461-466),
+    //     for (pKFi : vpTargetKFs) matcher.Fuse(pKFi, vpMapPointMatches);
+    // with the matcher of every (point, KeyFrame) pair in one launch (rsc_fuse_kf_many) and the bookkeeping
+    // of :690-695 and :797-817 replayed on the caller's objects, KeyFrame by KeyFrame and i ascending: isBad()
+    // and IsInKeyFrame(pKF) are read again at that moment, then GetMapPoint(bestIdx), Observations(), Replace in
+    // either direction (a tie takes the else branch) or AddObservation / AddMapPoint, and nFused counts as the
+    // reference does (a bad occupant counts).  The backward call (:490) is Fuse() after this one returned.
+    //
+    // Why launching every pair from the state at the call is exact (MapPoint.cpp:76-87, :158-197):
+    // (a) During SearchInNeighbors a good point only gains observations (AddObservation here and in Replace;
+    //     EraseObservation is not called) and a bad point stays bad (mbBad is only ever set).  So the set of
+    //     pairs that pass :695 only shrinks: a pair skipped at launch is skipped by the reference too, and a
+    //     pair that became ineligible since is dropped by the replay's own test.
+    // (b) Of what the matcher reads from a MapPoint (position, normal, min / max distance, descriptor) only the
+    //     descriptor can change between two Fuse calls: Replace ends with ComputeDistinctiveDescriptors() on
+    //     the survivor; the others change in UpdateNormalAndDepth, which SearchInNeighbors calls after both
+    //     directions (:493-506).  The uploaded descriptor bytes are kept; after every Replace the survivor's
+    //     GetDescriptor() is compared with them when the survivor is in the list, and once KeyFrame c is
+    //     replayed the changed points are matched again (a second small launch) against KeyFrames c + 1 ..
+    //     only, and their bestIdx patched.  Inside one Fuse call nothing is stale: the survivor is either pMP,
+    //     whose list position is behind the loop (and a repeated pointer to it is in pKF from now on), or
+    //     pMPinKF, which is in pKF and skipped by :695 for the rest of the call.
+    // The KeyFrames read nothing that Fuse changes (keypoints, pose, grid), so their views are uploaded once.
+    template <class KFPtr, class MPPtr>
+    std::vector<int> FuseMany(const std::vector<KFPtr>& vpTargetKFs, const std::vector<MPPtr>& vpMapPoints,
+                              float th = 3.0f) {
+        const int C = (int)vpTargetKFs.size();
+        std::vector<int> nFused(C, 0);
+        if (C == 0) return nFused;
+        // the list without its nulls (:692), in list order, which is the replay's order; repeated pointers stay
+        std::vector<MPPtr> pts;
+        for (size_t i = 0; i < vpMapPoints.size(); ++i)
+            if (vpMapPoints[i]) pts.push_back(vpMapPoints[i]);
+        const size_t np = pts.size();
+        std::vector<detail::KFViewUpload> views;
+        std::vector<int> ki;
+        upload_distinct(vpTargetKFs, views, ki);
+        {
+            std::vector<char> done(views.size(), 0);
+            for (int c = 0; c < C; ++c) {
+                if (done[ki[c]]) continue;
+                done[ki[c]] = 1;
+                const auto& K = *vpTargetKFs[c];
+                for (size_t l = 0; l < (size_t)K.mnScaleLevels; ++l) {  // ORBextractor.cpp:359,367
+                    const float sf = K.mvScaleFactors[l], s2 = sf * sf, inv = 1.0f / s2;
+                    if (l >= K.mvInvLevelSigma2.size() || !(K.mvInvLevelSigma2[l] == inv))
+                        throw std::runtime_error("rsc: Fuse: mvInvLevelSigma2 is not 1.0f / (mvScaleFactors^2)");
+                }
+                detail::set_triangulation(views[ki[c]], vpTargetKFs[c]);
+            }
+        }
+        detail::FusePoints up(np);
+        for (size_t j = 0; j < np; ++j) up.set(j, *pts[j]);
+        detail::MPViewUpload view = up.upload(np);
+        std::vector<std::vector<int32_t>> best(C, std::vector<int32_t>(np > 0 ? np : 1, -1));
+        fuse_kf_launch(vpTargetKFs, views, ki, 0, view.h, pts, th, best, nullptr);
+        std::vector<size_t> changed;  // entries whose descriptor a Replace of this KeyFrame's replay changed
+        auto survivor = [&](const MPPtr& s) {
+            bool read = false;
+            uint8_t now[32];
+            for (size_t j = 0; j < np; ++j) {
+                if (pts[j] != s) continue;
+                if (!read) {
+                    const auto d = s->GetDescriptor();
+                    const uint8_t* dr = d.template ptr<uint8_t>(0);
+                    std::copy(dr, dr + 32, now);
+                    read = true;
+                }
+                if (std::equal(now, now + 32, up.desc.begin() + 32 * j)) continue;
+                std::copy(now, now + 32, up.desc.begin() + 32 * j);
+                if (std::find(changed.begin(), changed.end(), j) == changed.end()) changed.push_back(j);
+            }
+        };
+        for (int c = 0; c < C; ++c) {
+            const KFPtr& pKF = vpTargetKFs[c];
+            for (size_t j = 0; j < np; ++j) {
+                const MPPtr& pMP = pts[j];
+                if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;  // :695, as it is now
+                const int bestIdx = best[c][j];
+                if (bestIdx < 0) continue;  // :798
+                MPPtr pMPinKF = pKF->GetMapPoint(bestIdx);
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) {
+                        if (pMPinKF->Observations() > pMP->Observations()) {
+                            pMP->Replace(pMPinKF);
+                            survivor(pMPinKF);
+                        } else {
+                            pMPinKF->Replace(pMP);
+                            survivor(pMP);
+                        }
+                    }
+                } else {
+                    pMP->AddObservation(pKF, bestIdx);
+                    pKF->AddMapPoint(pMP, bestIdx);
+                }
+                ++nFused[c];
+            }
+            if (!changed.empty() && c + 1 < C) {  // (b): the changed points against the KeyFrames still to come
+                std::sort(changed.begin(), changed.end());
+                detail::FusePoints sub(changed.size());
+                std::vector<MPPtr> spts;
+                for (size_t k = 0; k < changed.size(); ++k) {
+                    sub.copy(k, up, changed[k]);
+                    sub.state[k] = pts[changed[k]]->isBad() ? 2 : 1;
+                    spts.push_back(pts[changed[k]]);
+                }
+                detail::MPViewUpload sview = sub.upload(changed.size());
+                fuse_kf_launch(vpTargetKFs, views, ki, c + 1, sview.h, spts, th, best, &changed);
+            }
+            changed.clear();
+        }
+        return nFused;
+    }
+
     // SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cpp:16-100; Tracking.cpp:1027): every MapPoint with
     // mbTrackInView that is not bad is matched around (mTrackProjX, mTrackProjY) at levels
     // [mnTrackScaleLevel - 1, mnTrackScaleLevel]; the matches are written to F.mvpMapPoints, returns their
@@ -972,6 +1152,32 @@ private:
             }
             ki[c] = (int)j;
         }
+    }
+
+    // rsc_fuse_kf_many for KeyFrames c0 .. against the points of `view` (pts: its MapPoints), skip as it is now.
+    // The results go to best[c][j] or, with `at`, to best[c][(*at)[j]].
+    template <class KFPtr, class MPPtr>
+    static void fuse_kf_launch(const std::vector<KFPtr>& kfs, const std::vector<detail::KFViewUpload>& views,
+                               const std::vector<int>& ki, int c0, rsc_mpview* view, const std::vector<MPPtr>& pts,
+                               float th, std::vector<std::vector<int32_t>>& best, const std::vector<size_t>* at) {
+        const int C = (int)kfs.size() - c0;
+        const size_t np = pts.size();
+        std::vector<rsc_kfview*> hk(C);
+        std::vector<rsc_mpview*> hp(C, view);
+        std::vector<std::vector<uint8_t>> skip(C, std::vector<uint8_t>(np > 0 ? np : 1, 0));
+        std::vector<std::vector<int32_t>> out(C, std::vector<int32_t>(np > 0 ? np : 1, -1));
+        std::vector<const uint8_t*> ps(C);
+        std::vector<int32_t*> po(C);
+        for (int c = 0; c < C; ++c) {
+            hk[c] = views[ki[c0 + c]].h;
+            for (size_t j = 0; j < np; ++j) skip[c][j] = pts[j]->isBad() || pts[j]->IsInKeyFrame(kfs[c0 + c]) ? 1 : 0;
+            ps[c] = skip[c].data();
+            po[c] = out[c].data();
+        }
+        check(rsc_fuse_kf_many(thread_context(), hk.data(), hp.data(), C, ps.data(), th, po.data(), nullptr),
+              "Fuse(KeyFrame, vpMapPoints)");
+        for (int c = 0; c < C; ++c)
+            for (size_t j = 0; j < np; ++j) best[c0 + c][at ? (*at)[j] : j] = out[c][j];
     }
 
     template <class IsoT>

@@ -19,6 +19,7 @@
 #include "rsc_sim3opt.h"
 #include "rsc_orbmatch.h"
 #include "rsc_kfproj.h"
+#include "rsc_fusekf.h"
 #include "rsc_localproj.h"
 #include "rsc_kfdb.h"
 #include "rsc_bowvoc.h"
@@ -3513,6 +3514,84 @@ int rsc_fuse_sim3_many(rsc_context* C, rsc_kfview* const* kfs, int count, rsc_mp
     const char* h = C->h_fp.p;
     for (int c = 0; c < count; ++c) {
         const int32_t* b = reinterpret_cast<const int32_t*>(h + o_best + row4 * c);
+        int nf = 0;
+        for (int i = 0; i < np; ++i) {
+            best_idx[c][i] = b[i];
+            nf += b[i] >= 0;
+        }
+        if (nfused) nfused[c] = nf;
+    }
+    return RSC_OK;
+}
+
+// ---- LocalMapping::SearchInNeighbors: ORBmatcher::Fuse(pKF, vpMapPoints, th) (rsc_fusekf.h) ----
+int rsc_fuse_kf_many(rsc_context* C, rsc_kfview* const* kfs, rsc_mpview* const* points, int count,
+                     const uint8_t* const* skip, float th, int32_t* const* best_idx, int32_t* nfused) {
+    if (!C || count < 0 || count > 65535) return RSC_ERR_ARG;
+    if (count == 0) return RSC_OK;
+    if (!kfs || !points || !skip || !best_idx) return RSC_ERR_ARG;
+    if (!std::isfinite(th)) {
+        g_last_error = "non-finite th";
+        return RSC_ERR_ARG;
+    }
+    int max_points = 0;
+    for (int c = 0; c < count; ++c) {
+        if (int e = kfp_check_kf(C, kfs[c])) return e;
+        const rsc_kfview& k = *kfs[c];
+        if (!k.has_triang) {  // u_right, mbf and Ow
+            g_last_error = "a KeyFrame view without rsc_kfview_set_triangulation";
+            return RSC_ERR_ARG;
+        }
+        // the radius term of GetFeaturesInArea's cell arithmetic stays below 2^30 cells (rsc_search_by_sim3_many)
+        if (!(std::fabs(th) * k.top_scale * std::max(k.dev.gw_inv, k.dev.gh_inv) < 1073741824.0f)) {
+            g_last_error = "Fuse radius out of the grid arithmetic's range";
+            return RSC_ERR_ARG;
+        }
+        for (int i = 0; i < k.n; ++i)
+            if (k.octave[i] < 0 || k.octave[i] >= k.dev.n_levels) {  // the index of mvInvLevelSigma2
+                g_last_error = "KeyFrame keypoint octave out of range";
+                return RSC_ERR_ARG;
+            }
+        if (!points[c] || points[c]->ctx != C) return RSC_ERR_ARG;
+        if (points[c]->n && (!skip[c] || !best_idx[c])) return RSC_ERR_ARG;
+        max_points = std::max(max_points, points[c]->n);
+    }
+    // layout: problem table | skip flags  (uploaded)  | best_idx  (comes back); no scratch
+    std::vector<size_t> o_sk(count), o_best(count);
+    Arena A;
+    A.take(sizeof(FuseKfProblem) * count);
+    for (int c = 0; c < count; ++c) o_sk[c] = A.take((size_t)std::max(points[c]->n, 1));
+    A.end_upload();
+    A.end_scratch();
+    for (int c = 0; c < count; ++c) o_best[c] = A.take(4 * (size_t)std::max(points[c]->n, 1));
+    A.finish();
+    auto fill = [&](char* h, char* d) -> int {
+        for (int c = 0; c < count; ++c) {
+            const rsc_kfview& k = *kfs[c];
+            const rsc_mpview& m = *points[c];
+            if (m.n) std::memcpy(h + o_sk[c], skip[c], (size_t)m.n);
+            FuseKfProblem p;
+            p.K = kfp_kf_of(k);
+            p.P = m.dev;
+            std::memcpy(p.Rcw, k.R, sizeof(p.Rcw));
+            std::memcpy(p.tcw, k.t, sizeof(p.tcw));
+            std::memcpy(p.Ow, k.tri.Ow, sizeof(p.Ow));
+            p.mbf = k.tri.mbf;
+            p.u_right = k.tri.u_right;
+            p.skip = reinterpret_cast<const uint8_t*>(d + o_sk[c]);
+            p.best_idx = reinterpret_cast<int32_t*>(d + o_best[c]);
+            std::memcpy(h + sizeof(FuseKfProblem) * c, &p, sizeof(p));
+        }
+        return 0;
+    };
+    auto launch = [&](char* d) {
+        return launch_fuse_kf(count, max_points, reinterpret_cast<const FuseKfProblem*>(d), th, C->stream);
+    };
+    if (int e = arena_run(C, C->d_fp, C->h_fp, A, fill, launch, /*download=*/max_points != 0)) return e;
+    const char* h = C->h_fp.p;
+    for (int c = 0; c < count; ++c) {
+        const int np = points[c]->n;
+        const int32_t* b = reinterpret_cast<const int32_t*>(h + o_best[c]);
         int nf = 0;
         for (int i = 0; i < np; ++i) {
             best_idx[c][i] = b[i];

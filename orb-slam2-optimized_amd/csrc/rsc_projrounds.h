@@ -64,6 +64,24 @@ __device__ __forceinline__ int proj_first_min_coop(const DevProjFrame& F, int ce
     return (int)(best >> 32) <= cutoff ? (int)(best & 0xffff) : -1;
 }
 
+// proj_first_min_coop for a matcher without claims (every feature free, KfpAllFree: the KeyFrame Fuse of
+// rsc_fusekf.h): the gate alone decides what takes part
+template <int kSub, class Gate>
+__device__ __forceinline__ int proj_first_min_free_coop(const DevProjFrame& F, int cells, const ProjDesc dMP,
+                                                        const Gate& gate, int cutoff, int lane) {
+    const ProjDesc* desc = F.desc;
+    unsigned long long best = kProjNoKey;
+    if (cells >= 0)
+        best = proj_walk_coop<kSub>(F, ProjCells(cells), lane, best, [&](unsigned long long k, int f, int rank) {
+            if (!gate(f)) return k;
+            const unsigned long long key = proj_coop_key(proj_desc_dist(dMP, desc[f]), rank, f);
+            return key < k ? key : k;
+        });
+    best = proj_min_coop<kSub>(best);
+    if (best == kProjNoKey) return -1;
+    return (int)(best >> 32) <= cutoff ? (int)(best & 0xffff) : -1;
+}
+
 // The rounds of one workgroup of kThreads lanes (the loop and its bound: rsc_projcore.h).  owner: the LDS
 // table over the n_features features; claim: A, -1 on entry; n_eligible: the points with a window.  M is the
 // matcher:

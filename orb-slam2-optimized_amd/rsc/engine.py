@@ -63,7 +63,7 @@ EXPORTED = [
     "rsc_lastframe_create", "rsc_lastframe_destroy", "rsc_search_by_projection_last_many",
     "rsc_track_motion_model_many",
     "rsc_kfview_set_triangulation", "rsc_search_for_triangulation_many", "rsc_triangulate_pairs_many",
-    "rsc_create_new_map_points_many",
+    "rsc_create_new_map_points_many", "rsc_fuse_kf_many",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -616,6 +616,20 @@ def fuse_sim3_many(ctx: Context, kfs, points, Scw, in_kf, th: float):
     return [b[:points.n] for b in best], nf[:c]
 
 
+def fuse_kf_many(ctx: Context, kfs, points, skip, th: float):
+    """ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cpp:671-821), the matcher of
+    LocalMapping::SearchInNeighbors, for each (KFView with set_triangulation, MPView, skip uint8 [points n] =
+    isBad() || IsInKeyFrame(pKF)) in one launch; `points` may name one MPView several times.  Returns (list of
+    best_idx int32 [points n], nfused int32[count]); the bookkeeping of :797-817 stays with the caller."""
+    c = len(kfs)
+    sk = [np.ascontiguousarray(a, np.uint8) if p.n else np.zeros(1, np.uint8) for a, p in zip(skip, points)]
+    best = [np.full(max(p.n, 1), -7, np.int32) for p in points]
+    nf = np.zeros(max(c, 1), np.int32)
+    _check(load_library().rsc_fuse_kf_many(ctx.h, _handles(kfs), _handles(points), c, _ptrs(sk), float(th),
+                                           _ptrs(best), nf), "rsc_fuse_kf_many")
+    return [b[:p.n] for b, p in zip(best, points)], nf[:c]
+
+
 def loop_verify_many(ctx: Context, kf_cur, kf_matched, loop_points, S, matches, already):
     """The closing stage of LoopClosing::ComputeSim3 (LoopClosing.cpp:318-320, :360-370;
     rsc_loop_verify_many) on the result of the gated loop events: S [count][8] = LoopGateResult.S,
@@ -967,6 +981,8 @@ def load_library(path: str = LIB_PATH):
                                                    C.POINTER(C.c_void_p), i32p, i32p]
     L.rsc_fuse_sim3_many.argtypes = [vp, C.POINTER(vp), C.c_int, vp, f32p_, C.POINTER(C.c_void_p), C.c_float,
                                      C.POINTER(C.c_void_p), i32p]
+    L.rsc_fuse_kf_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(C.c_void_p), C.c_float,
+                                   C.POINTER(C.c_void_p), i32p]
     L.rsc_loop_verify_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, f64p_,
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                        C.POINTER(LoopVerifyResult), C.POINTER(C.c_void_p)]
