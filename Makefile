@@ -11,7 +11,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
-     facade_lastproj_test facade_triang_test arena_test rounds_test triang_emu fusekf_emu facade_fusekf_test
+     facade_lastproj_test facade_triang_test arena_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -23,6 +23,15 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 $(LIBDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+
+# kernels.hip with the compiler's kernel-resource remarks kept beside the object; anything else the compiler says
+# (warnings) is shown as usual, without source excerpts (registers, scratch and
+# waves per SIMD of every kernel as built: tests/test_cpu_round_args_resources.py)
+$(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -fno-caret-diagnostics -c $< -o $@ \
+		2> $(LIBDIR)/kernels.resources.txt || { cat $(LIBDIR)/kernels.resources.txt >&2; exit 1; }
+	@grep -v 'Rpass-analysis=kernel-resource-usage' $(LIBDIR)/kernels.resources.txt >&2 || true
 
 $(LIBDIR)/librsc.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
@@ -84,6 +93,21 @@ $(LIBDIR)/rounds_test_san: $(ROUNDS_DEPS)
 	mkdir -p $(LIBDIR)
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
 
+# TEST-ONLY host programs: the closed form of srand(seed)'s window (rsc_core.h rng_seed_word) against
+# the Schrage loop, and RngStream's seed mark and lazily worked-out window (tests/test_cpu_seed_window.py);
+# the second build runs under the host sanitizers
+seed_window_test: $(LIBDIR)/seed_window_test $(LIBDIR)/seed_window_test_san
+
+SEED_WINDOW_DEPS = tests/cpp/seed_window_test.cpp $(CSRC)/rsc_core.h $(CSRC)/rsc_engine.h
+
+$(LIBDIR)/seed_window_test: $(SEED_WINDOW_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/seed_window_test_san: $(SEED_WINDOW_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -116,4 +140,4 @@ clean:
 	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build
 
 .PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
-        facade_voc_test chase_mirror_test arena_test rounds_test clean
+        facade_voc_test chase_mirror_test arena_test rounds_test seed_window_test clean

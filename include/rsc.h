@@ -67,6 +67,16 @@ int rsc_context_set_eig_rows(rsc_context* ctx, int max_workgroups);
  * split form — the QR chase and the Q rotations on two waves of one SIMD (pnp_eig_split_kernel) — or
  * 0 the lane-pair form (pnp_eig_group_kernel).  Both are bit-identical. */
 int rsc_context_set_eig_split(rsc_context* ctx, int on);
+/* Descriptor path of the PnP speculation round (no effect on results): 1 (default; env
+ * RSC_ROUND_ARGS) the round's per-solver records travel in the kernels' argument blocks, the 31-word
+ * rand() windows follow from the seeds on the device and the problem table stays resident between
+ * rounds (uploaded only when it changes); 0 every round uploads its descriptors as one blob.  Rounds
+ * of more than 64 solvers, and rounds with a solver whose rand() window has moved off its seed (or
+ * that is bound to a shared stream), take the blob path whatever the setting. */
+int rsc_context_set_round_args(rsc_context* ctx, int on);
+/* Diagnostic: PnP speculation rounds of the context so far on [0] the argument path, [1] the blob
+ * path, and [2] uploads of the resident problem table. */
+int rsc_diag_round_paths(rsc_context* ctx, int64_t out[3]);
 /* Form of rsc_optimize_sim3_many (no effect on results): helpers > 0 runs each pair on one master
  * workgroup plus that many helper workgroups that evaluate the edges' numeric Jacobians in chunks
  * (the cooperative form); 0 one workgroup per pair; -1 (default; env RSC_SO_HELPERS) as many helpers

@@ -76,39 +76,42 @@ namespace rsc {
 // PnP hypotheses, two-kernel form (rsc_quad.h): lane-group eigenvectors (kEigLanes lanes per
 // hypothesis, kEigHyps per workgroup, one wave per SIMD), then one wave per beta approximation.
 // ------------------------------------------------------------------------------------------------
-template <int NS>
+// A (every kernel of the round): NoRoundArgs (the records are lps, in HBM) or RoundArgs (the records by
+// value in the argument block; lps is null), rsc_quad.h round_rec
+template <int NS, class A>
 __global__ __launch_bounds__(64) void pnp_eig_group_kernel(const DevPnP* __restrict__ probs,
                                                           const LaunchProb* __restrict__ lps,
                                                           const int2* __restrict__ wg_table,
                                                           const uint32_t* __restrict__ rng_T,
-                                                          double* __restrict__ stage, int32_t* __restrict__ samples) {
+                                                          double* __restrict__ stage, int32_t* __restrict__ samples,
+                                                          const A args) {
     __shared__ __attribute__((aligned(16))) double smem[kEigHyps * kQuadRegion];
-    pnp_eig_group_body<NS, 99, kEigLanes, kEigHyps>(probs, lps, wg_table, rng_T, stage, samples, smem);
+    pnp_eig_group_body<NS, 99, kEigLanes, kEigHyps>(probs, lps, wg_table, rng_T, stage, samples, smem, args);
 }
 
 // split form (rsc_quad.h pnp_eig_split_body): wave 0 chases, wave 1 rotates Q
 // (<= 256 registers: two waves per SIMD, so a SIMD holds a chase wave and its row wave)
-template <int NS>
+template <int NS, class A>
 __global__ __launch_bounds__(128 * kSplitUnits) __attribute__((amdgpu_waves_per_eu(2))) void pnp_eig_split_kernel(
     const DevPnP* __restrict__ probs, const LaunchProb* __restrict__ lps, const int2* __restrict__ wg_table,
     int nwg_table, const uint32_t* __restrict__ rng_T, double* __restrict__ stage, int32_t* __restrict__ samples,
-    unsigned* fault) {
+    unsigned* fault, const A args) {
     __shared__ __attribute__((aligned(16))) double smem[kSplitHyps * kQuadRegion];
     __shared__ __attribute__((aligned(16))) double dsub[kSplitHyps * kSplitDsub];
     __shared__ int pub[kSplitUnits], ack[kSplitUnits];
-    pnp_eig_split_body<NS>(probs, lps, wg_table, nwg_table, rng_T, stage, samples, smem, dsub, pub, ack, fault);
+    pnp_eig_split_body<NS>(probs, lps, wg_table, nwg_table, rng_T, stage, samples, smem, dsub, pub, ack, fault, args);
 }
 
-template <int NS>
+template <int NS, class A>
 __global__ __launch_bounds__(64) void pnp_betas_kernel(const DevPnP* __restrict__ probs,
                                                        const LaunchProb* __restrict__ lps,
                                                        const int2* __restrict__ wg_table, int ngroups,
                                                        const double* __restrict__ stage,
                                                        const int32_t* __restrict__ samples,
                                                        double* __restrict__ berr, float* __restrict__ bpose,
-                                                       size_t hcap, int hb) {
+                                                       size_t hcap, int hb, const A args) {
     __shared__ __attribute__((aligned(16))) double smem[kBetasWaveSmemDoubles];
-    pnp_betas_wave_body<NS>(probs, lps, wg_table, ngroups, hb, stage, samples, berr, bpose, hcap, smem);
+    pnp_betas_wave_body<NS>(probs, lps, wg_table, ngroups, hb, stage, samples, berr, bpose, hcap, smem, args);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -145,7 +148,7 @@ __device__ __forceinline__ void pnp_inlier2(const float (&R)[9], const float (&t
     in1 = e2.y < maxErr.y;
 }
 
-template <int PPT>
+template <int PPT, class A>
 __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict__ probs,
                                                        const LaunchProb* __restrict__ lps,
                                                        const int4* __restrict__ wg_table,  // lp, hyp0, count
@@ -155,7 +158,7 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
                                                        int32_t* __restrict__ counts,
                                                        int32_t* __restrict__ counts_dev,
                                                        uint64_t* __restrict__ masks, int mask_words,
-                                                       int32_t* __restrict__ qual) {
+                                                       int32_t* __restrict__ qual, const A args) {
     // Hypotheses per flush: the 4 waves' counts of a batch wait in LDS until the batch's totals are
     // summed.  The only inlier mask of a round's problem that is ever read is the one of its FIRST
     // hypothesis reaching mRansacMinInliers: the replay pauses there (rsc_engine.h
@@ -171,7 +174,7 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
     __shared__ int first_sh;  // the chunk's first qualifying hypothesis, -1: none (set by every flush)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int4 wt = wg_table[blockIdx.x];
-    const LaunchProb& lp = lps[wt.x];
+    const auto& lp = round_rec(lps, args, wt.x);
     const DevPnP& P = probs[lp.prob];
     const double fx = P.fx, fy = P.fy, cx = P.cx, cy = P.cy;
     // The hypothesis' pose is the betas stage's approximation with the smallest error, in the
@@ -368,14 +371,15 @@ static_assert(kRefineEigLanes == 2 || kRefineEigLanes == 4, "refine eigen group:
 
 // Eigen stage in the Refine's rows form for small launches (rsc_quad.h pnp_eig_rows_body; A/B
 // variant behind RSC_EIG_ROWS): same workgroup table and stage records as pnp_eig_group_kernel.
-template <int NS>
+template <int NS, class A>
 __global__ __launch_bounds__(256) void pnp_eig_rows_kernel(const DevPnP* __restrict__ probs,
                                                            const LaunchProb* __restrict__ lps,
                                                            const int2* __restrict__ wg_table,
                                                            const uint32_t* __restrict__ rng_T,
-                                                           double* __restrict__ stage, int32_t* __restrict__ samples) {
+                                                           double* __restrict__ stage, int32_t* __restrict__ samples,
+                                                           const A args) {
     __shared__ __attribute__((aligned(16))) double smem[kEigHyps * kRowsRegion];
-    pnp_eig_rows_body<NS, kRefineEigLanes>(probs, lps, wg_table, rng_T, stage, samples, smem, [] { wave_lds_sync(); });
+    pnp_eig_rows_body<NS, kRefineEigLanes>(probs, lps, wg_table, rng_T, stage, samples, smem, [] { wave_lds_sync(); }, args);
 }
 
 #if RSC_FOLD_PIPE
@@ -921,14 +925,22 @@ __global__ __launch_bounds__(256) void pnp_refine_kernel(const DevPnP* __restric
 // set_maximum_number_of_correspondences(max(rows0, mnBestInliers)).  The host replay applies the
 // same rules to the same counts and takes these results (RefineSelOut) instead of launching the
 // refine itself; a solver without a qualifying hypothesis leaves k = -1 and touches nothing.
+// SA: NoRoundArgs (the records are sels, in HBM) or SelArgs (the records by value in the argument block, the
+// last parameter; sels is null).
+__device__ __forceinline__ const RefineSel& sel_rec(const RefineSel* __restrict__ sels, const NoRoundArgs&, int i) {
+    return sels[i];
+}
+__device__ __forceinline__ const RefineSel& sel_rec(const RefineSel*, const SelArgs& a, int i) { return a.s[i]; }
+template <class SA>
 __global__ __launch_bounds__(256) void pnp_select_refine_kernel(const DevPnP* __restrict__ probs,
                                                                 const RefineSel* __restrict__ sels,
                                                                 const int32_t* __restrict__ counts,
                                                                 uint64_t* __restrict__ masks, int mask_words,
                                                                 const float* __restrict__ poses,
-                                                                RefineSelOut* __restrict__ out, unsigned* fault) {
+                                                                RefineSelOut* __restrict__ out, unsigned* fault,
+                                                                const SA sel_args) {
     __shared__ int k_sh;
-    const RefineSel S = sels[blockIdx.x];
+    const RefineSel S = sel_rec(sels, sel_args, blockIdx.x);
     const int tid = threadIdx.x;
     if (tid < 64) {
         int k = -1;
@@ -1167,44 +1179,66 @@ __global__ void rng_stream_kernel(const uint32_t* __restrict__ T, Window31 w, in
 // ------------------------------------------------------------------------------------------------
 // The rows-form eigen stage exists only for the 20-hypothesis workgroup (4 waves x 5 twelve-lane
 // groups); builds with another RSC_EIG_HYPS compile without it and refuse the variant.
-template <int N>
-static hipError_t launch_eig_rows(int nwgE, const int2* wgtE, const DevPnP* probs, const LaunchProb* lps,
+template <int N, class A>
+static hipError_t launch_eig_rows(int nwgE, const int2* wgtE, const DevPnP* probs, const LaunchProb* lps, const A& args,
                                   const uint32_t* T, double* stage, int32_t* samples, hipStream_t st) {
     if constexpr (kEigHyps == 4 * kRowsGroups) {
-        pnp_eig_rows_kernel<N><<<nwgE, 256, 0, st>>>(probs, lps, wgtE, T, stage, samples);
+        pnp_eig_rows_kernel<N, A><<<nwgE, 256, 0, st>>>(probs, lps, wgtE, T, stage, samples, args);
         return hipSuccess;
     } else {
         return hipErrorInvalidValue;
     }
 }
 
+// The explicit arguments of the round's kernels beside the records: at most 12 pointers / sizes and
+// one int (pnp_scan_kernel), 8-byte aligned; pnp_select_refine_kernel has 8 and one int.
+static_assert(sizeof(RoundArgs) + 13 * 8 + kHiddenArgBytes <= kKernArgLimit,
+              "RoundArgs: the largest launch's argument block must stay within HIP's limit");
+static_assert(sizeof(SelArgs) + 9 * 8 + kHiddenArgBytes <= kKernArgLimit,
+              "SelArgs: pnp_select_refine_kernel's argument block must stay within HIP's limit");
+
+template <int N, class A>
+static hipError_t launch_solve_ns(int nwgE, const int2* wgtE, int nwgB, const int2* wgtB, const DevPnP* probs,
+                                  const LaunchProb* lps, const A& args, const uint32_t* T, double* stage,
+                                  int32_t* samples, const BetasScratch& bs, hipStream_t st, hipEvent_t eig_end,
+                                  bool eig_rows, bool eig_split, unsigned* fault, int betas_hb) {
+    if (eig_rows) {
+        const hipError_t e = launch_eig_rows<N, A>(nwgE, wgtE, probs, lps, args, T, stage, samples, st);
+        if (e != hipSuccess) return e;
+    } else if (eig_split)
+        pnp_eig_split_kernel<N, A><<<(nwgE + kSplitUnits - 1) / kSplitUnits, 128 * kSplitUnits, 0, st>>>(
+            probs, lps, wgtE, nwgE, T, stage, samples, fault, args);
+    else
+        pnp_eig_group_kernel<N, A><<<nwgE, 64, 0, st>>>(probs, lps, wgtE, T, stage, samples, args);
+    if (eig_end) (void)hipEventRecord(eig_end, st);
+    pnp_betas_kernel<N, A><<<3 * nwgB, 64, 0, st>>>(probs, lps, wgtB, nwgB, stage, samples, bs.err, bs.pose, bs.hcap,
+                                                    betas_hb, args);
+    return hipSuccess;
+}
+
 hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, const int2* wgtB,
-                                  const DevPnP* probs, const LaunchProb* lps, const uint32_t* T, double* stage,
-                                  int32_t* samples, const BetasScratch& bs, hipStream_t st,
-                                  hipEvent_t eig_begin, hipEvent_t eig_end, bool eig_rows, bool eig_split,
-                                  unsigned* fault, int betas_hb) {
+                                  const DevPnP* probs, const LaunchProb* lps, const RoundArgs* args,
+                                  const uint32_t* T, double* stage, int32_t* samples, const BetasScratch& bs,
+                                  hipStream_t st, hipEvent_t eig_begin, hipEvent_t eig_end, bool eig_rows,
+                                  bool eig_split, unsigned* fault, int betas_hb) {
     if (ns < 4 || ns > 6 || betas_hb < 1 || betas_hb > kBetasHyps) return hipErrorInvalidValue;
     if (eig_split && !eig_rows && !fault) return hipErrorInvalidValue;
+    if (!lps && !args) return hipErrorInvalidValue;
     if (eig_begin) (void)hipEventRecord(eig_begin, st);
+    hipError_t e = hipSuccess;
     switch (ns) {
-#define RSC_CASE(N)                                                                                   \
-    case N:                                                                                           \
-        if (eig_rows) {                                                                               \
-            const hipError_t e = launch_eig_rows<N>(nwgE, wgtE, probs, lps, T, stage, samples, st);   \
-            if (e != hipSuccess) return e;                                                            \
-        } else if (eig_split)                                                                         \
-            pnp_eig_split_kernel<N><<<(nwgE + kSplitUnits - 1) / kSplitUnits, 128 * kSplitUnits, 0, st>>>( \
-                probs, lps, wgtE, nwgE, T, stage, samples, fault);                                    \
-        else                                                                                          \
-            pnp_eig_group_kernel<N><<<nwgE, 64, 0, st>>>(probs, lps, wgtE, T, stage, samples);        \
-        if (eig_end) (void)hipEventRecord(eig_end, st);                                               \
-        pnp_betas_kernel<N><<<3 * nwgB, 64, 0, st>>>(probs, lps, wgtB, nwgB, stage, samples,          \
-                                                     bs.err, bs.pose, bs.hcap, betas_hb);             \
+#define RSC_CASE(N)                                                                                              \
+    case N:                                                                                                      \
+        e = args ? launch_solve_ns<N>(nwgE, wgtE, nwgB, wgtB, probs, nullptr, *args, T, stage, samples, bs, st,  \
+                                      eig_end, eig_rows, eig_split, fault, betas_hb)                             \
+                 : launch_solve_ns<N>(nwgE, wgtE, nwgB, wgtB, probs, lps, NoRoundArgs{}, T, stage, samples, bs,  \
+                                      st, eig_end, eig_rows, eig_split, fault, betas_hb);                        \
         break;
         RSC_CASE(4) RSC_CASE(5) RSC_CASE(6)
 #undef RSC_CASE
         default: return hipErrorInvalidValue;
     }
+    if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
@@ -1331,11 +1365,21 @@ hipError_t launch_selftest_math(int fn, const double* x, int n, double* out, hip
     return hipGetLastError();
 }
 
-hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const int4* wgt,
-                           const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks,
-                           int mask_words, int32_t* qual, hipStream_t st) {
+hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const RoundArgs* args,
+                           const int4* wgt, const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev,
+                           uint64_t* masks, int mask_words, int32_t* qual, hipStream_t st) {
+    if (!lps && !args) return hipErrorInvalidValue;
     switch (ppt) {
-#define RSC_CASE(P) case P: pnp_scan_kernel<P><<<nwg, 256, 0, st>>>(probs, lps, wgt, bs.err, bs.pose, bs.hcap, poses, counts, counts_dev, masks, mask_words, qual); break;
+#define RSC_CASE(P)                                                                                                  \
+    case P:                                                                                                          \
+        if (args)                                                                                                    \
+            pnp_scan_kernel<P, RoundArgs><<<nwg, 256, 0, st>>>(probs, nullptr, wgt, bs.err, bs.pose, bs.hcap, poses, \
+                                                               counts, counts_dev, masks, mask_words, qual, *args); \
+        else                                                                                                         \
+            pnp_scan_kernel<P, NoRoundArgs><<<nwg, 256, 0, st>>>(probs, lps, wgt, bs.err, bs.pose, bs.hcap, poses,   \
+                                                                 counts, counts_dev, masks, mask_words, qual,       \
+                                                                 NoRoundArgs{});                                    \
+        break;
         RSC_CASE(1) RSC_CASE(2) RSC_CASE(4) RSC_CASE(8) RSC_CASE(16) RSC_CASE(32)
 #undef RSC_CASE
         default: return hipErrorInvalidValue;
@@ -1343,9 +1387,10 @@ hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchPr
     return hipGetLastError();
 }
 
+// the argument-path instantiation has the same registers and LDS (tests/test_cpu_round_args_resources.py)
 hipError_t pnp_scan_occupancy(int ppt, int* wgs_per_cu) {
     switch (ppt) {
-#define RSC_CASE(P) case P: return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, reinterpret_cast<const void*>(&pnp_scan_kernel<P>), 256, 0);
+#define RSC_CASE(P) case P: return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, reinterpret_cast<const void*>(&pnp_scan_kernel<P, NoRoundArgs>), 256, 0);
         RSC_CASE(1) RSC_CASE(2) RSC_CASE(4) RSC_CASE(8) RSC_CASE(16) RSC_CASE(32)
 #undef RSC_CASE
         default: return hipErrorInvalidValue;
@@ -1366,12 +1411,17 @@ hipError_t launch_pnp_refine(int njobs, const DevPnP* probs, const RefineJob* jo
     return hipGetLastError();
 }
 
-hipError_t launch_pnp_select_refine(int nsel, const DevPnP* probs, const RefineSel* sels, const int32_t* counts,
-                                    uint64_t* masks, int mask_words, const float* poses, RefineSelOut* out,
-                                    unsigned* fault, hipStream_t st) {
+hipError_t launch_pnp_select_refine(int nsel, const DevPnP* probs, const RefineSel* sels, const SelArgs* sel_args,
+                                    const int32_t* counts, uint64_t* masks, int mask_words, const float* poses,
+                                    RefineSelOut* out, unsigned* fault, hipStream_t st) {
     if (nsel <= 0) return hipSuccess;
-    if (!fault) return hipErrorInvalidValue;
-    pnp_select_refine_kernel<<<nsel, 256, 0, st>>>(probs, sels, counts, masks, mask_words, poses, out, fault);
+    if (!fault || (!sels && !sel_args) || (sel_args && nsel > kRoundArgsCap)) return hipErrorInvalidValue;
+    if (sel_args)
+        pnp_select_refine_kernel<SelArgs><<<nsel, 256, 0, st>>>(probs, nullptr, counts, masks, mask_words, poses, out,
+                                                                fault, *sel_args);
+    else
+        pnp_select_refine_kernel<NoRoundArgs><<<nsel, 256, 0, st>>>(probs, sels, counts, masks, mask_words, poses, out,
+                                                                    fault, NoRoundArgs{});
     return hipGetLastError();
 }
 

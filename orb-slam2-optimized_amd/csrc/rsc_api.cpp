@@ -204,20 +204,26 @@ struct Blob {
     }
 };
 
-int upload_blob(rsc_context* C, const Blob& b) {
-    const size_t n16 = (b.bytes.size() + 15) / 16;
+// n bytes through the pinned staging to dst (device memory with room for n rounded up to 16), in
+// stream order with the launches that read them
+int upload_bytes(rsc_context* C, const void* src, size_t n, void* dst) {
+    const size_t n16 = (n + 15) / 16;
     if (int e = C->h_desc.ensure(n16 * 16)) return e;
-    if (int e = C->d_desc.ensure(n16 * 16)) return e;
     // the previous round's upload must be finished before the pinned staging is overwritten
     RSC_HIP(hipStreamSynchronize(C->stream));
-    std::memcpy(C->h_desc.p, b.bytes.data(), b.bytes.size());
+    std::memcpy(C->h_desc.p, src, n);
     // a copy kernel on the context stream, not hipMemcpyAsync: the DMA engine's start-up and its
     // completion hand-off to the first kernel cost ~15 us per round (rocprofv3 copy + kernel trace)
     if (C->dma_upload)
-        RSC_HIP(hipMemcpyAsync(C->d_desc.p, C->h_desc.p, b.bytes.size(), hipMemcpyHostToDevice, C->stream));
+        RSC_HIP(hipMemcpyAsync(dst, C->h_desc.p, n, hipMemcpyHostToDevice, C->stream));
     else
-        RSC_HIP(launch_upload16(C->h_desc.p, C->d_desc.p, n16, C->stream));
+        RSC_HIP(launch_upload16(C->h_desc.p, dst, n16, C->stream));
     return 0;
+}
+
+int upload_blob(rsc_context* C, const Blob& b) {
+    if (int e = C->d_desc.ensure((b.bytes.size() + 15) / 16 * 16)) return e;
+    return upload_bytes(C, b.bytes.data(), b.bytes.size(), C->d_desc.p);
 }
 
 // Inlier counts of a speculation round: written by the scan kernel straight into pinned host
@@ -334,6 +340,7 @@ struct HipPnPBackend : PnPBackend {
     }
     DevPnP dev_of(rsc_pnp* p) {
         DevPnP d;
+        std::memset(&d, 0, sizeof(d));  // padding too: the resident table is compared by its bytes
         d.pts = p->d_pts;
         d.uv = p->d_uv;
         d.n = p->st.N;
@@ -354,22 +361,38 @@ struct HipPnPBackend : PnPBackend {
         std::vector<LaunchProb>& lps = lps_tl;
         probs.resize(count);
         lps.resize(count);
+        // The argument path: the round's records travel in the kernels' argument blocks and the windows
+        // follow from the seeds on the device, which holds only while every solver still stands on its
+        // seed window (a moved window or a shared stream's position exists as 31 words alone).
+        bool use_args = C->round_args && count <= kRoundArgsCap;
+        thread_local std::vector<rsc_pnp*> ps_tl;  // of(S[i]) is a search: once per solver and round
+        std::vector<rsc_pnp*>& ps = ps_tl;
+        ps.resize(count);
         for (int i = 0; i < count; ++i) {
-            rsc_pnp* p = of(S[i]);
-            if (!p) return RSC_ERR_ARG;
+            ps[i] = of(S[i]);
+            if (!ps[i]) return RSC_ERR_ARG;
             if (S[i]->mRansacMinSet < 4 || S[i]->mRansacMinSet > 6) {
                 g_last_error = "min_set outside the supported range [4,6]";
                 return RSC_ERR_UNSUPPORTED;
             }
             S[i]->rng.ensure(C->table, H[i] * S[i]->mRansacMinSet);
+            use_args = use_args && S[i]->rng.on_seed_window;
+        }
+        thread_local RoundArgs ra_tl;
+        RoundArgs& ra = ra_tl;
+        for (int i = 0; i < count; ++i) {
+            rsc_pnp* p = ps[i];
             probs[i] = dev_of(p);
             LaunchProb& lp = lps[i];
             lp.prob = i;
             lp.H = H[i];
             lp.out0 = total;
             lp.g0 = S[i]->rng.g;
-            std::memcpy(lp.window, S[i]->rng.window, sizeof(lp.window));
             lp.min_inliers = S[i]->mRansacMinInliers;  // only such hypotheses' masks are ever read
+            if (use_args)
+                ra.r[i] = RoundRec{i, H[i], total, lp.g0, lp.min_inliers, S[i]->rng.seed_value};
+            else
+                std::memcpy(lp.window, S[i]->rng.words(), sizeof(lp.window));  // works the words out if need be
             p->spec_out0 = total;
             p->spec_H = H[i];
             total += H[i];
@@ -389,7 +412,7 @@ struct HipPnPBackend : PnPBackend {
         std::vector<RefineSel>& sels = sels_tl;
         sels.resize(fused ? count : 0);
         for (int i = 0; fused && i < count; ++i) {
-            rsc_pnp* p = of(S[i]);
+            rsc_pnp* p = ps[i];
             RefineSel& r = sels[i];
             r.prob = i;
             r.out0 = lps[i].out0;
@@ -495,11 +518,41 @@ struct HipPnPBackend : PnPBackend {
             RSC_HIP(hipStreamSynchronize(C->stream));
             C->pnp_tab_key = key;
         }
-        Blob b;
-        const size_t o_probs = b.add(probs.data(), probs.size() * sizeof(DevPnP));
-        const size_t o_lps = b.add(lps.data(), lps.size() * sizeof(LaunchProb));
-        const size_t o_sel = fused ? b.add(sels.data(), sels.size() * sizeof(RefineSel)) : 0;
-        if (int e = upload_blob(C, b)) return e;
+        const DevPnP* dprobs = nullptr;
+        const LaunchProb* dlps = nullptr;
+        const RefineSel* dsels = nullptr;
+        thread_local SelArgs sa_tl;
+        SelArgs& sa = sa_tl;
+        if (use_args) {
+            // The problem table changes only when SetRansacParameters, a Refine (rows, buffers) or the
+            // solver set changes it: it stays on the device, and a round whose table equals the mirror
+            // uploads nothing.  The previous round (the table's last reader) has finished.
+            std::vector<DevPnP>& mirror = C->pnp_probs_host;
+            const size_t pbytes = probs.size() * sizeof(DevPnP);
+            if (mirror.size() != probs.size() || !C->d_pnp_probs.p ||
+                std::memcmp(mirror.data(), probs.data(), pbytes) != 0) {
+                mirror.clear();  // invalid until the upload below is enqueued
+                if (int e = C->d_pnp_probs.ensure(probs.size() + 1)) return e;  // the copy moves whole 16-B words
+                if (int e = upload_bytes(C, probs.data(), pbytes, C->d_pnp_probs.p)) return e;
+                mirror.assign(probs.begin(), probs.end());
+                ++C->n_probs_uploads;
+            }
+            dprobs = C->d_pnp_probs.p;
+            for (int i = 0; fused && i < count; ++i) sa.s[i] = sels[i];
+            ++C->n_rounds_args;
+        } else {
+            Blob b;
+            const size_t o_probs = b.add(probs.data(), probs.size() * sizeof(DevPnP));
+            const size_t o_lps = b.add(lps.data(), lps.size() * sizeof(LaunchProb));
+            const size_t o_sel = fused ? b.add(sels.data(), sels.size() * sizeof(RefineSel)) : 0;
+            if (int e = upload_blob(C, b)) return e;
+            const char* base = C->d_desc.p;
+            dprobs = reinterpret_cast<const DevPnP*>(base + o_probs);
+            dlps = reinterpret_cast<const LaunchProb*>(base + o_lps);
+            dsels = reinterpret_cast<const RefineSel*>(base + o_sel);
+            ++C->n_rounds_blob;
+        }
+        const RoundArgs* dargs = use_args ? &ra : nullptr;
         const char* tab = C->d_pnp_tab.p;
         if (int e = C->d_poses.ensure((size_t)total * 12)) return e;
         int32_t* cnt_dst = nullptr;
@@ -523,9 +576,6 @@ struct HipPnPBackend : PnPBackend {
         if (int e = C->d_berr.ensure((size_t)total * 3)) return e;
         if (int e = C->d_bpose.ensure((size_t)total * 36)) return e;
         const BetasScratch bs{C->d_berr.p, C->d_bpose.p, (size_t)total};
-        const char* base = C->d_desc.p;
-        const DevPnP* dprobs = reinterpret_cast<const DevPnP*>(base + o_probs);
-        const LaunchProb* dlps = reinterpret_cast<const LaunchProb*>(base + o_lps);
         host_mark(C, 0);
         timing_begin(C, 0);
         bool first_group = true;
@@ -536,19 +586,20 @@ struct HipPnPBackend : PnPBackend {
             RSC_HIP(launch_pnp_solve_split(4 + g, (int)quad_wgs[g].size(),
                                           reinterpret_cast<const int2*>(tab + C->pnp_tab_quad[g]), (int)solve_wgs[g].size(),
                                           reinterpret_cast<const int2*>(tab + C->pnp_tab_solve[g]), dprobs, dlps,
-                                          C->d_table.p, C->d_stage.p, C->d_samples.p, bs, C->stream,
+                                          dargs, C->d_table.p, C->d_stage.p, C->d_samples.p, bs, C->stream,
                                           eb, C->timing ? C->ev[7 + 2 * g] : nullptr,
                                           (int)quad_wgs[g].size() <= C->eig_rows_max_wgs, C->eig_split,
                                           C->h_flag + kFaultWord, hb));
             first_group = false;
         }
         timing_begin(C, 1);
-        RSC_HIP(launch_pnp_scan(ppt, (int)scan_wgs.size(), dprobs, dlps, reinterpret_cast<const int4*>(tab + C->pnp_tab_scan),
+        RSC_HIP(launch_pnp_scan(ppt, (int)scan_wgs.size(), dprobs, dlps, dargs,
+                                reinterpret_cast<const int4*>(tab + C->pnp_tab_scan),
                                 bs, C->d_poses.p, cnt_dst, cnt_dev, C->d_masks.p, mw, C->h_qual.p, C->stream));
         timing_begin(C, 2);
         if (fused) {
             timing_begin(C, 3);
-            RSC_HIP(launch_pnp_select_refine(count, dprobs, reinterpret_cast<const RefineSel*>(base + o_sel),
+            RSC_HIP(launch_pnp_select_refine(count, dprobs, dsels, use_args ? &sa : nullptr,
                                              cnt_dev ? cnt_dev : cnt_dst, C->d_masks.p, mw, C->d_poses.p,
                                              C->d_selout.p, C->h_flag + kFaultWord, C->stream));
             timing_begin(C, 4);
@@ -749,7 +800,7 @@ struct HipSim3Backend : Sim3Backend {
             lp.prob = i; lp.H = H[i]; lp.out0 = total; lp.g0 = S[i]->rng.g;
             lp.min_inliers = S[i]->mRansacMinInliers;  // the pick kernel's return rule
             lp.best0 = S[i]->mnBestInliers;
-            std::memcpy(lp.window, S[i]->rng.window, sizeof(lp.window));
+            std::memcpy(lp.window, S[i]->rng.words(), sizeof(lp.window));
             p->spec_out0 = total;
             p->spec_H = H[i];
             total += H[i];
@@ -911,7 +962,7 @@ struct HipMLBackend : MLBackend {
             lp.H = H[i];
             lp.out0 = total;
             lp.g0 = S[i]->rng.g;
-            std::memcpy(lp.window, S[i]->rng.window, sizeof(lp.window));
+            std::memcpy(lp.window, S[i]->rng.words(), sizeof(lp.window));
             lp.min_inliers = S[i]->mRansacMinInliers;  // only such hypotheses' masks are ever read
             p->spec_out0 = total;
             p->spec_H = H[i];
@@ -1114,6 +1165,7 @@ int rsc_context_create(int device, rsc_context** out) {
     if (const char* m = std::getenv("RSC_EIG_SPLIT")) C->eig_split = std::strcmp(m, "0") != 0;
     if (const char* m = std::getenv("RSC_BETAS_HB")) C->betas_small_hb = std::min(kBetasHyps, std::max(1, std::atoi(m)));
     if (const char* m = std::getenv("RSC_SPIN_WAIT")) C->spin_wait = std::strcmp(m, "0") != 0;
+    if (const char* m = std::getenv("RSC_ROUND_ARGS")) C->round_args = std::strcmp(m, "0") != 0;
     if (const char* m = std::getenv("RSC_SO_HELPERS")) C->so_helpers = std::max(-1, std::atoi(m));
     {
         void* f = nullptr;
@@ -1170,6 +1222,20 @@ int rsc_context_set_eig_rows(rsc_context* C, int max_workgroups) {
 int rsc_context_set_eig_split(rsc_context* C, int on) {
     if (!C) return RSC_ERR_ARG;
     C->eig_split = on != 0;
+    return RSC_OK;
+}
+
+int rsc_context_set_round_args(rsc_context* C, int on) {
+    if (!C) return RSC_ERR_ARG;
+    C->round_args = on != 0;
+    return RSC_OK;
+}
+
+int rsc_diag_round_paths(rsc_context* C, int64_t out[3]) {
+    if (!C || !out) return RSC_ERR_ARG;
+    out[0] = C->n_rounds_args;
+    out[1] = C->n_rounds_blob;
+    out[2] = C->n_probs_uploads;
     return RSC_OK;
 }
 
@@ -3059,7 +3125,7 @@ int rsc_rand_stream(rsc_context* C, uint32_t seed, int n, int32_t* out) {
     while (done < n) {
         const int chunk = std::min(8192, n - done);
         r.ensure(C->table, chunk);
-        RSC_HIP(launch_rng_stream(C->d_table.p, r.window, r.g, chunk, d.p, C->stream));
+        RSC_HIP(launch_rng_stream(C->d_table.p, r.words(), r.g, chunk, d.p, C->stream));
         RSC_HIP(hipMemcpyAsync(out + done, d.p, (size_t)chunk * 4, hipMemcpyDeviceToHost, C->stream));
         RSC_HIP(hipStreamSynchronize(C->stream));
         r.g += chunk;
@@ -3075,6 +3141,7 @@ int rsc_stream_create(rsc_context* C, uint32_t seed, rsc_stream** out) {
     rsc_stream* s = new rsc_stream();
     s->ctx = C;
     s->st.seed(seed);
+    s->st.drop_seed_mark();  // bound solvers copy this position: a shared stream is always its words
     *out = s;
     return RSC_OK;
 }
@@ -3105,7 +3172,7 @@ int rsc_stream_peek(rsc_stream* s, int n, int32_t* out) {
     for (int done = 0; done < n;) {
         const int chunk = std::min(8192, n - done);
         r.ensure(C->table, chunk);
-        RSC_HIP(launch_rng_stream(C->d_table.p, r.window, r.g, chunk, d.p, C->stream));
+        RSC_HIP(launch_rng_stream(C->d_table.p, r.words(), r.g, chunk, d.p, C->stream));
         RSC_HIP(hipMemcpyAsync(out + done, d.p, (size_t)chunk * 4, hipMemcpyDeviceToHost, C->stream));
         RSC_HIP(hipStreamSynchronize(C->stream));
         r.g += chunk;

@@ -1121,6 +1121,38 @@ RSC_HD uint32_t rng_word(const uint32_t* __restrict__ T /* [g][32] */, const uin
     return acc;
 }
 
+// The window srand(seed) defines (RngStream::seed: r[0..30] by Schrage's steps, r[31..33] = r[0..2],
+// window[j] = r[3 + j]) in closed form, one word at a time: r[i] = r0 * 16807^i mod (2^31 - 1).
+//   * r0 is taken as seed() takes it: 0 -> 1, and a seed >= 2^31 is a negative int32;
+//   * r[0] is r0 itself, unreduced (it may be negative or 2^31 - 1);
+//   * a Schrage step computes 16807 r - 2147483647 (r / 127773) in int32 and adds the modulus once
+//     when that is negative.  For every int32 r0 the result lies in [0, 2^31 - 1): from r[1] on the
+//     words are the true residues, which is what the 64-bit product's remainder gives.
+// The 31 powers are compile-time constants, so a word costs one 64-bit multiply and remainder instead
+// of up to 30 dependent steps: the kernels derive a round's window from the 4-byte seed (one lane per
+// word, rsc_quad.h round_window) and the host materialises it only when something reads it.
+struct MinstdPowers {
+    uint32_t p[31];
+};
+constexpr MinstdPowers minstd_powers() {
+    MinstdPowers t{};
+    uint64_t x = 1;
+    for (int i = 0; i < 31; ++i) {
+        t.p[i] = (uint32_t)x;
+        x = x * 16807u % 2147483647u;
+    }
+    return t;
+}
+RSC_HD uint32_t rng_seed_word(uint32_t seed, int j /* [0, 31) */) {
+    constexpr MinstdPowers P = minstd_powers();
+    const int i = j < 28 ? j + 3 : j - 28;
+    const int32_t r0 = (seed == 0) ? 1 : (int32_t)seed;
+    if (i == 0) return (uint32_t)r0;
+    int64_t x = (int64_t)r0 * (int64_t)P.p[i] % (int64_t)2147483647;
+    if (x < 0) x += 2147483647;
+    return (uint32_t)x;
+}
+
 // DUtils::Random::RandomInt(0, size-1) given the raw word.
 RSC_HD int random_index(uint32_t word, int size) {
     const int32_t r = (int32_t)(word >> 1);

@@ -11,9 +11,11 @@
 //      buffer state; a successful one ends the call.
 // The backend interface is implemented by the HIP backend (rsc_api.cpp).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include <algorithm>
 
@@ -48,24 +50,58 @@ struct RngTable {
     }
 };
 
+// srand(seed): r[0..30] by Schrage, r[31..33] = r[0..2]; window = r[3..33] (m = 34).
+inline void rng_seed_window(uint32_t s, uint32_t (&w)[31]) {
+    int32_t r[34];
+    r[0] = (s == 0) ? 1 : (int32_t)s;
+    for (int i = 1; i < 31; ++i) {
+        int32_t hi = r[i - 1] / 127773, lo = r[i - 1] % 127773;
+        int32_t word = 16807 * lo - 2836 * hi;
+        if (word < 0) word += 2147483647;
+        r[i] = word;
+    }
+    for (int i = 31; i < 34; ++i) r[i] = r[i - 31];
+    for (int j = 0; j < 31; ++j) w[j] = (uint32_t)r[3 + j];
+}
+
+// The 31 words of an RngStream.  seed() stores only the seed; the words are worked out when
+// something reads them, which every read does by converting the member to a pointer (the stream is
+// reached through its first member, see RngStream).  A round whose solvers all still stand on their
+// seed windows hands the kernels the seeds (rsc_core.h rng_seed_word) and never reads them.
+struct RngStream;
+struct RngWindow {
+    mutable uint32_t w[31] = {};
+    inline operator const uint32_t*() const;
+
+private:
+    // only ever a member of an RngStream (its first): the conversion above relies on it
+    RngWindow() = default;
+    RngWindow(const RngWindow&) = default;
+    RngWindow& operator=(const RngWindow&) = default;
+    friend struct RngStream;
+};
+
 struct RngStream {
-    uint32_t window[31];
+    RngWindow window;  // FIRST member: RngWindow's conversion finds the stream's seed through it
     int g;  // draws already consumed, relative to the window
-    // srand(seed): r[0..30] by Schrage, r[31..33] = r[0..2]; window = r[3..33] (m = 34) and the
-    // first output r[344] is draw g = 310.
+    uint32_t seed_value = 0;   // meaningful while on_seed_window
+    bool on_seed_window = false;  // the window is still the one seed() defined: ensure / rebase / advance have not moved it
+    mutable bool have_words = true;  // false: seeded, the words are not worked out yet
+    // srand(seed): the window of rng_seed_window and the first output r[344] is draw g = 310.
     void seed(uint32_t s) {
-        int32_t r[34];
-        r[0] = (s == 0) ? 1 : (int32_t)s;
-        for (int i = 1; i < 31; ++i) {
-            int32_t hi = r[i - 1] / 127773, lo = r[i - 1] % 127773;
-            int32_t word = 16807 * lo - 2836 * hi;
-            if (word < 0) word += 2147483647;
-            r[i] = word;
-        }
-        for (int i = 31; i < 34; ++i) r[i] = r[i - 31];
-        for (int j = 0; j < 31; ++j) window[j] = (uint32_t)r[3 + j];
+        seed_value = s;
+        on_seed_window = true;
+        have_words = false;
         g = 310;
     }
+    // Forget the seed: the stream is its 31 words from here on (a shared stream, whose position the
+    // bound solvers copy, is always in this state).
+    void drop_seed_mark() {
+        (void)words();
+        on_seed_window = false;
+    }
+    // the 31 words, worked out first if the stream was seeded and not read since
+    const uint32_t* words() const { return window; }
     // Move the window forward so that `need` more draws stay addressable by the table:
     // new window = r[m+g-31 .. m+g-1], new m = m+g, next draw 0.
     void ensure(const RngTable& tab, int need) {
@@ -73,12 +109,14 @@ struct RngStream {
         rebase(tab);
     }
     void rebase(const RngTable& tab) {  // requires g <= kRngTableRows
+        const uint32_t* w = words();
         uint32_t nw[31];
         for (int j = 0; j < 31; ++j) {
             const int x = g - 31 + j;
-            nw[j] = (x >= 0) ? tab.word(window, x) : window[31 + x];
+            nw[j] = (x >= 0) ? tab.word(w, x) : w[31 + x];
         }
-        std::memcpy(window, nw, sizeof(nw));
+        std::memcpy(window.w, nw, sizeof(nw));
+        on_seed_window = false;
         g = 0;
     }
     // Skip n draws of the stream (any n >= 0): the window is re-based once per table reach, so a
@@ -93,6 +131,18 @@ struct RngStream {
         }
     }
 };
+static_assert(std::is_standard_layout<RngStream>::value && offsetof(RngStream, window) == 0,
+              "RngWindow reaches its stream as the stream's first member");
+static_assert(sizeof(RngWindow) == 31 * sizeof(uint32_t), "the window is its 31 words");
+
+inline RngWindow::operator const uint32_t*() const {
+    const RngStream* s = reinterpret_cast<const RngStream*>(this);
+    if (!s->have_words) {
+        rng_seed_window(s->seed_value, w);
+        s->have_words = true;
+    }
+    return w;
+}
 
 constexpr int kMaxSpeculate = 4000;  // hypotheses per solver per launch round
 

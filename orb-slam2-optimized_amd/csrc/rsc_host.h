@@ -103,6 +103,16 @@ struct rsc_context {
     DevBuf<char> d_pnp_tab;
     std::vector<int> pnp_tab_key;
     size_t pnp_tab_quad[3] = {0, 0, 0}, pnp_tab_solve[3] = {0, 0, 0}, pnp_tab_scan = 0;
+    // The PnP round's DevPnP table, resident next to the work tables (the argument path of speculate()):
+    // `pnp_probs_host` mirrors what d_pnp_probs holds, and a round whose table equals it uploads nothing.
+    DevBuf<DevPnP> d_pnp_probs;
+    std::vector<DevPnP> pnp_probs_host;
+    // Round records as kernel arguments and the resident table (default), or every round's
+    // descriptors through the blob; env RSC_ROUND_ARGS=0/1, rsc_context_set_round_args
+    bool round_args = true;
+    // diagnostic counters (rsc_diag_round_paths): rounds on the argument path, rounds on the blob path,
+    // uploads of the resident problem table
+    int64_t n_rounds_args = 0, n_rounds_blob = 0, n_probs_uploads = 0;
     // resident pnp_scan_kernel<PPT> workgroups of the device, [log2 PPT] (occupancy query x CU count,
     // read at the first round that needs it; 0: not read yet)
     int pnp_scan_capacity[6] = {0, 0, 0, 0, 0, 0};

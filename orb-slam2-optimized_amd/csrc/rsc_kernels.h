@@ -50,6 +50,22 @@ struct LaunchProb {
     int best0 = 0;    // Sim3 pick: mnBestInliers when the call started
 };
 
+// A PnP round's record per solver as a kernel argument (the default path, rsc_api.cpp speculate()):
+// what the kernels read of LaunchProb besides the window, and the seed the window follows from
+// (rsc_core.h rng_seed_word; only rounds whose solvers all stand on their seed windows take this path).
+struct RoundRec {
+    int prob, H, out0, g0, min_inliers;
+    uint32_t seed;
+};
+// Solvers per round on the argument path; a larger round takes the blob path.  The runtime copies a
+// launch's whole argument block at every launch, so the capacity is paid by every round: 64 is the
+// headline's candidate count (config 2) and 1.5 KB per launch.
+constexpr int kRoundArgsCap = 64;
+struct RoundArgs {
+    RoundRec r[kRoundArgsCap];
+};
+struct NoRoundArgs {};  // the kernels' `args` on the blob path: the records are read from HBM
+
 // Sim3 pick (sim3_pick_kernel): hypotheses per solver it can hold in LDS.
 constexpr int kPickMaxH = 4096;
 
@@ -86,6 +102,14 @@ struct RefineSelOut {
     float pose[12];      // refined R (9) + t (3)
     float best_pose[12]; // adopted hypothesis pose (when adopt)
 };
+
+// pnp_select_refine_kernel's records of a round on the argument path
+struct SelArgs {
+    RefineSel s[kRoundArgsCap];
+};
+// HIP's limit on a launch's argument block, and what the runtime appends to the explicit arguments
+// (the hidden arguments: grid offsets, printf / heap / queue pointers)
+constexpr size_t kKernArgLimit = 4096, kHiddenArgBytes = 256;
 
 struct Window31 {
     uint32_t w[31];
@@ -138,10 +162,12 @@ constexpr int kBetasHyps = RSC_BETAS_HYPS;
 // workgroups run the rows form.
 constexpr int kEigRowsDefaultWgs = 64;
 hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, const int2* wgtB,
-                                  const DevPnP* probs, const LaunchProb* lps, const uint32_t* T, double* stage,
-                                  int32_t* samples, const BetasScratch& bs, hipStream_t st,
+                                  const DevPnP* probs, const LaunchProb* lps, const RoundArgs* args,
+                                  const uint32_t* T, double* stage, int32_t* samples, const BetasScratch& bs, hipStream_t st,
                                   hipEvent_t eig_begin = nullptr, hipEvent_t eig_end = nullptr, bool eig_rows = false,
                                   bool eig_split = false, unsigned* fault = nullptr, int betas_hb = kBetasHyps);
+// lps / args: the round's records in HBM (blob path) or, when args is non-null, by value in the
+// kernels' argument blocks (lps is then not read).
 // betas_hb: hypotheses per betas wave (<= kBetasHyps; the wg_table's groups step by it).
 // fault (required by the split form): a word in pinned host memory that the split eigen stage sets to
 // 1 when a chase / row-wave hand-off gives up (split_wait); the host turns it into RSC_ERR_INTERNAL.
@@ -150,14 +176,16 @@ hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, 
 // launch problem lp reaches its min_inliers.
 // bs: the betas stage's results; the scan keeps each hypothesis' approximation with the smallest error
 // (a scan workgroup's chunk holds at most 64 hypotheses) and writes its pose to poses[record].
-hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const int4* wgt,
-                           const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks,
+hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const RoundArgs* args,
+                           const int4* wgt, const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks,
                            int mask_words, int32_t* qual, hipStream_t st);
 // Workgroups of pnp_scan_kernel<ppt> one CU holds at once (the runtime's occupancy query for the
 // instantiated kernel: registers and LDS as built).
 hipError_t pnp_scan_occupancy(int ppt, int* wgs_per_cu);
 // fault: the context's fault word (the Refine's split-form eigen hand-off, RSC_REFINE_SPLIT)
-hipError_t launch_pnp_select_refine(int nsel, const DevPnP* probs, const RefineSel* sels, const int32_t* counts,
+// sels: the records in HBM, or null with sel_args: by value in the argument block
+hipError_t launch_pnp_select_refine(int nsel, const DevPnP* probs, const RefineSel* sels, const SelArgs* sel_args,
+                                    const int32_t* counts,
                                     uint64_t* masks, int mask_words, const float* poses, RefineSelOut* out,
                                     unsigned* fault, hipStream_t st);
 // Rounds up to this many hypotheses run the replay's first Refine on the device right after the

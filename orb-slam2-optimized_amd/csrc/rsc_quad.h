@@ -17,6 +17,7 @@
 // restatement (rsc_core.h / oracle), so results are bitwise identical; the only reorderings are of
 // independent scalars (and of max(), which is order-free for the non-NaN case handled below).
 #pragma once
+#include <type_traits>
 #include "rsc_core.h"
 #include "rsc_epnp.h"
 #include "rsc_kernels.h"
@@ -390,6 +391,28 @@ __device__ __forceinline__ void rows_eig12_ev4(double* T, double* E, int lane, S
     RSC_EIG_PHASE(3);
 }
 
+// ------------------------------------------------------------------------------------------------
+// A round's per-solver record, from either source: the launch records in HBM (blob path: `lps`, and
+// NoRoundArgs for `args`) or the kernel's own argument block (RoundArgs by value; lps is not read).
+// The table entry that indexes them is wave-uniform, so both are scalar loads; the argument block is
+// indexed where it lies (no private copy).  Both record types name the fields the kernels read alike.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ const LaunchProb& round_rec(const LaunchProb* __restrict__ lps, const NoRoundArgs&, int i) {
+    return lps[i];
+}
+__device__ __forceinline__ const RoundRec& round_rec(const LaunchProb*, const RoundArgs& a, int i) { return a.r[i]; }
+// The solver's 31-word window, uniform over the wave.  Blob path: the record's words.  Argument
+// path: lane j of the wave works out word j from the seed (rng_seed_word: one multiply and one
+// remainder) and the words are then read lane by lane into scalar registers, where the blob path's
+// scalar loads put them.  Lanes 0..30 of the calling wave must be active.
+__device__ __forceinline__ void round_window(const LaunchProb& lp, int, uint32_t (&w)[31]) {
+    RSC_UNROLL for (int j = 0; j < 31; ++j) w[j] = lp.window[j];
+}
+__device__ __forceinline__ void round_window(const RoundRec& r, int wave_lane, uint32_t (&w)[31]) {
+    const uint32_t mine = rng_seed_word(r.seed, wave_lane < 31 ? wave_lane : 30);
+    RSC_UNROLL for (int j = 0; j < 31; ++j) w[j] = (uint32_t)__builtin_amdgcn_readlane((int)mine, j);
+}
+
 // Kernel 1 of the two-kernel hypothesis solve: sample, control points, alphas, MtM, and the 12x12
 // eigenvectors, L lanes per hypothesis (a lane group), HPW hypotheses per 64-lane workgroup
 // (HPW * L <= 64; lanes beyond leave at once).  Writes the stage record (eigenvectors, alphas, cws)
@@ -402,17 +425,19 @@ __device__ __forceinline__ void rows_eig12_ev4(double* T, double* E, int lane, S
 // 1,024 SIMDs — the last 176 SIMDs run two waves back to back — but 960 pair waves of 20
 // hypotheses (kEigHyps), one per SIMD; 32 per pair wave (600 waves) leaves SIMDs idle at the same
 // per-wave latency (tools/qr_bench).
-template <int NS, int STOP, int L, int HPW>
+template <int NS, int STOP, int L, int HPW, class RA = NoRoundArgs>
 __device__ __forceinline__ void pnp_eig_group_body(const DevPnP* __restrict__ probs, const LaunchProb* __restrict__ lps,
                                                    const int2* __restrict__ wg_table, const uint32_t* __restrict__ rng_T,
                                                    double* __restrict__ stage, int32_t* __restrict__ samples,
-                                                   double* smem) {
+                                                   double* smem, const RA& args = RA{}) {
     static_assert(HPW * L <= 64 && (L == 2 || L == 4), "lane groups of 2 or 4 within one wave");
+    static_assert(!std::is_same<RA, RoundArgs>::value || HPW * L >= 31,
+                  "argument path: lanes 0..30 work out the window words (round_window), so they must stay");
     constexpr int RJ = 12 / L;
     const int lane = threadIdx.x, g = lane / L, q = lane % L;
     if (g >= HPW) return;  // whole groups only: the DPP broadcasts never read a departed lane
     const int2 wt = wg_table[blockIdx.x];
-    const LaunchProb& lp = lps[wt.x];
+    const auto& lp = round_rec(lps, args, wt.x);
     const bool active = wt.y + g < lp.H;
     const int h = active ? wt.y + g : lp.H - 1;  // idle groups repeat the last hypothesis (no writes)
     const DevPnP& P = probs[lp.prob];
@@ -426,7 +451,7 @@ __device__ __forceinline__ void pnp_eig_group_body(const DevPnP* __restrict__ pr
     {
         int idx[NS];
         uint32_t w[31];
-        RSC_UNROLL for (int j = 0; j < 31; ++j) w[j] = lp.window[j];
+        round_window(lp, lane, w);
         uint32_t words[NS];
         RSC_UNROLL for (int d = 0; d < NS; ++d) words[d] = rng_word(rng_T, w, lp.g0 + h * NS + d);
         swap_remove_sample<NS>(words, NS, P.n, idx);
@@ -568,16 +593,16 @@ __device__ __forceinline__ void pnp_eig_group_body(const DevPnP* __restrict__ pr
 // form (rows_eig12_ev4 is group_eig12_ev4's arithmetic).  Needs kEigHyps * kRowsRegion doubles.
 constexpr int kRowsGroups = 5;                    // 12-lane groups per wave
 constexpr int kRowsRegion = kQuadT + 90 + 1;      // T, E (rows_eig12_ev4: >= 90 doubles), odd pad
-template <int NS, int L, class Sync>
+template <int NS, int L, class Sync, class RA = NoRoundArgs>
 __device__ __forceinline__ void pnp_eig_rows_body(const DevPnP* __restrict__ probs, const LaunchProb* __restrict__ lps,
                                                   const int2* __restrict__ wg_table, const uint32_t* __restrict__ rng_T,
                                                   double* __restrict__ stage, int32_t* __restrict__ samples,
-                                                  double* smem, Sync sync) {
+                                                  double* smem, Sync sync, const RA& args = RA{}) {
     static_assert(kEigHyps == 4 * kRowsGroups, "4 waves of 5 twelve-lane groups per workgroup");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / 12, r = lane - 12 * g;
     if (g >= kRowsGroups) return;  // lanes 60..63: whole groups only
     const int2 wt = wg_table[blockIdx.x];
-    const LaunchProb& lp = lps[wt.x];
+    const auto& lp = round_rec(lps, args, wt.x);
     const int slot = kRowsGroups * wave + g;
     if (wt.y + kRowsGroups * wave >= lp.H) return;  // a wave without hypotheses (no cross-wave sync below)
     const bool active = wt.y + slot < lp.H;
@@ -607,7 +632,7 @@ __device__ __forceinline__ void pnp_eig_rows_body(const DevPnP* __restrict__ pro
     {
         int idx[NS];
         uint32_t w[31];
-        RSC_UNROLL for (int j = 0; j < 31; ++j) w[j] = lp.window[j];
+        round_window(lp, lane, w);
         uint32_t words[NS];
         RSC_UNROLL for (int d = 0; d < NS; ++d) words[d] = rng_word(rng_T, w, lp.g0 + h * NS + d);
         swap_remove_sample<NS>(words, NS, P.n, idx);
@@ -833,12 +858,12 @@ __device__ __forceinline__ void refine_eig12_rows(const double* T, const double*
     }
 }
 
-template <int NS>
+template <int NS, class RA = NoRoundArgs>
 __device__ __forceinline__ void pnp_eig_split_body(const DevPnP* __restrict__ probs, const LaunchProb* __restrict__ lps,
                                                    const int2* __restrict__ wg_table, int nwg_table,
                                                    const uint32_t* __restrict__ rng_T, double* __restrict__ stage,
                                                    int32_t* __restrict__ samples, double* smem, double* dsub,
-                                                   int* pub, int* ack, unsigned* fault) {
+                                                   int* pub, int* ack, unsigned* fault, const RA& args = RA{}) {
     constexpr int HPW = kEigHyps, U = kSplitUnits;
     static_assert(HPW == 20 && 2 * HPW <= 64 && 4 * HPW <= 128 && HPW * kSplitRowLanes <= 64, "unit layout");
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -847,7 +872,7 @@ __device__ __forceinline__ void pnp_eig_split_body(const DevPnP* __restrict__ pr
     const int entry = blockIdx.x * U + unit;
     const bool unit_ok = entry < nwg_table;  // the last workgroup may hold fewer units
     const int2 wt = wg_table[unit_ok ? entry : 0];
-    const LaunchProb& lp = lps[wt.x];
+    const auto& lp = round_rec(lps, args, wt.x);
     const DevPnP& P = probs[lp.prob];
     double* Tu = smem + unit * HPW * kQuadRegion;  // the unit's 20 regions
     double* Du = dsub + unit * HPW * kSplitDsub;
@@ -872,7 +897,7 @@ __device__ __forceinline__ void pnp_eig_split_body(const DevPnP* __restrict__ pr
         double* T = Tu + g * kQuadRegion;
         int idx[NS];
         uint32_t w[31];
-        RSC_UNROLL for (int j = 0; j < 31; ++j) w[j] = lp.window[j];
+        round_window(lp, lane, w);
         uint32_t words[NS];
         RSC_UNROLL for (int d = 0; d < NS; ++d) words[d] = RSC_DIAG_NO_RNG ? (uint32_t)(2654435761u * (uint32_t)(h * NS + d + 1)) : rng_word(rng_T, w, lp.g0 + h * NS + d);
         swap_remove_sample<NS>(words, NS, P.n, idx);
@@ -1058,18 +1083,18 @@ RSC_HD void betas_block(int b, int ngroups, int& g, int& apx) {
 // of a group neither count arrivals nor wait for each other.
 // hb: hypotheses per wave (64 for large rounds; fewer for small ones, so a wave carries the union
 // of fewer data-dependent chains): lanes >= hb mirror lane % hb (same control flow, no writes).
-template <int NS>
+template <int NS, class RA = NoRoundArgs>
 __device__ __forceinline__ void pnp_betas_wave_body(const DevPnP* __restrict__ probs, const LaunchProb* __restrict__ lps,
                                                     const int2* __restrict__ wg_table, int ngroups, int hb,
                                                     const double* __restrict__ stage,
                                                     const int32_t* __restrict__ samples,
                                                     double* __restrict__ berr, float* __restrict__ bpose,
-                                                    size_t hcap, double* smem) {
+                                                    size_t hcap, double* smem, const RA& args = RA{}) {
     const int lane = threadIdx.x;
     int g, apx;
     betas_block(blockIdx.x, ngroups, g, apx);
     const int2 wt = wg_table[g];
-    const LaunchProb& lp = lps[wt.x];
+    const auto& lp = round_rec(lps, args, wt.x);
     const bool active = lane < hb && wt.y + lane < lp.H;
     const int hm = wt.y + lane % hb;
     const int h = active ? wt.y + lane : (hm < lp.H ? hm : wt.y);

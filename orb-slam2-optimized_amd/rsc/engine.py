@@ -31,6 +31,7 @@ EXPORTED = [
     "rsc_version", "rsc_status_string", "rsc_context_create", "rsc_context_destroy", "rsc_context_set_stream",
     "rsc_context_synchronize", "rsc_context_last_timing", "rsc_context_last_kernel_timing", "rsc_diag_host_timing", "rsc_context_enable_timing", "rsc_selftest_math",
     "rsc_context_set_eig_rows", "rsc_context_set_eig_split", "rsc_context_set_sim3opt_helpers",
+    "rsc_context_set_round_args", "rsc_diag_round_paths",
     "rsc_pnp_create", "rsc_pnp_destroy", "rsc_pnp_set_ransac_parameters", "rsc_pnp_iterate", "rsc_pnp_find",
     "rsc_pnp_last_inliers",
     "rsc_pnp_iterate_many", "rsc_pnp_reset", "rsc_pnp_get_state", "rsc_pnp_last_samples", "rsc_pnp_last_hypotheses",
@@ -856,6 +857,8 @@ def load_library(path: str = LIB_PATH):
     L.rsc_diag_host_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.rsc_context_enable_timing.argtypes = [vp, C.c_int]
     L.rsc_context_set_eig_rows.argtypes = [vp, C.c_int]
+    L.rsc_context_set_round_args.argtypes = [vp, C.c_int]
+    L.rsc_diag_round_paths.argtypes = [vp, C.POINTER(C.c_int64)]
     L.rsc_context_set_eig_split.argtypes = [vp, C.c_int]
     L.rsc_context_set_sim3opt_helpers.argtypes = [vp, C.c_int]
     L.rsc_pnp_create.argtypes = [vp, C.POINTER(PnPProblem), C.c_uint32, C.POINTER(vp)]
@@ -1061,6 +1064,18 @@ class Context:
         """Split-form eigen stage (chase and Q rotations on two waves) for the launches the rows form
         does not take (default on); off: the lane-pair form."""
         _check(load_library().rsc_context_set_eig_split(self.h, int(bool(on))), "set_eig_split")
+
+    def set_round_args(self, on: bool):
+        """PnP rounds with their records as kernel arguments and the problem table resident on the
+        device (default on); off: every round uploads its descriptor blob."""
+        _check(load_library().rsc_context_set_round_args(self.h, int(bool(on))), "set_round_args")
+
+    def round_paths(self):
+        """Diagnostic counters of the context's PnP rounds: on the argument path, on the blob path,
+        and uploads of the resident problem table."""
+        out = (C.c_int64 * 3)()
+        _check(load_library().rsc_diag_round_paths(self.h, out), "round_paths")
+        return dict(args=int(out[0]), blob=int(out[1]), table_uploads=int(out[2]))
 
     def set_sim3opt_helpers(self, helpers: int):
         """OptimizeSim3's form: helper workgroups per pair (the cooperative form), 0 = one workgroup
