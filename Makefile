@@ -11,7 +11,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
-     facade_lastproj_test facade_triang_test arena_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test
+     facade_lastproj_test facade_triang_test arena_test viewimage_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -79,6 +79,20 @@ $(LIBDIR)/arena_test_san: tests/cpp/arena_test.cpp $(CSRC)/rsc_arena.h
 	mkdir -p $(LIBDIR)
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
 
+# TEST-ONLY host programs: the view-image builder and the views' shared argument checks against the view
+# builders' former offset arithmetic (tests/test_cpu_viewimage.py); the second build runs under the host sanitizers
+viewimage_test: $(LIBDIR)/viewimage_test $(LIBDIR)/viewimage_test_san
+
+VIEWIMAGE_DEPS = tests/cpp/viewimage_test.cpp $(CSRC)/rsc_viewimage.h $(CSRC)/rsc_arena.h include/rsc.h
+
+$(LIBDIR)/viewimage_test: $(VIEWIMAGE_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/viewimage_test_san: $(VIEWIMAGE_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 # TEST-ONLY host programs: the drivers' bookkeeping (rsc_rounds.h) against the former driver loops
 # (tests/test_cpu_rounds.py); the second build runs under the host sanitizers
 rounds_test: $(LIBDIR)/rounds_test $(LIBDIR)/rounds_test_san
@@ -140,4 +154,4 @@ clean:
 	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build
 
 .PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
-        facade_voc_test chase_mirror_test arena_test rounds_test seed_window_test clean
+        facade_voc_test chase_mirror_test arena_test viewimage_test rounds_test seed_window_test clean

@@ -1,5 +1,7 @@
-// rsc_host.h — librsc's private header: what rsc_api.cpp (backends, matchers, staging) and
-// rsc_drivers.cpp (the entry points that only compose other ABI calls) share.  Not installed.
+// rsc_host.h — librsc's private header: what the translation units of the C ABI share (rsc_api.cpp: context,
+// backends and solvers; rsc_optim.cpp, rsc_views.cpp, rsc_matchers.cpp, rsc_voc.cpp, rsc_kfdb.cpp by
+// subsystem; rsc_drivers.cpp: the entry points that only compose other ABI calls): the opaque handle
+// structs, RSC_HIP, the buffers, and the staging helpers of the batched calls.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -11,6 +13,10 @@
 #include "rsc_frameproj.h"
 #include "rsc_lastproj.h"
 #include "rsc_triang.h"
+#include "rsc_kfdb.h"
+#include "rsc_bowvoc.h"
+#include "rsc_arena.h"
+#include "rsc_viewimage.h"
 
 using namespace rsc;
 #pragma GCC visibility push(hidden)  // what this block declares stays out of the library's exported symbols
@@ -243,6 +249,11 @@ struct rsc_kfview {
     float R[9], t[3], K[4];
     float top_scale = 1.0f;  // mvScaleFactors[n_levels - 1] (the largest search radius is th times it)
     DevSim3KF dev;           // the header as uploaded (device pointers), for SearchByProjection's problem table
+    // what the problem tables copy of an immutable view, built once: the KeyFrame of the loop-closing and Fuse
+    // matchers (no rotation check: angle null) and of the Frame matcher (angle: rsc_kfview_set_angles)
+    DevKfpKF kfp;
+    DevProjKF proj;
+    bool octaves_ok = false;  // every keypoint octave is in [0, dev.n_levels)
     DevBuf<float> d_angle;   // mvKeysUn[i].angle (rsc_kfview_set_angles)
     bool has_angles = false;
     // rsc_kfview_set_triangulation: kp_raw | u_right | depth | cos_stereo on the device, the view as the pair
@@ -251,7 +262,6 @@ struct rsc_kfview {
     TriView tri;
     std::vector<float> h_uright;
     float Kinv[9];
-    int n_levels = 0;
     bool has_triang = false;
 };
 
@@ -282,6 +292,115 @@ struct rsc_lastframe {
     std::vector<float> mp_pos;
 };
 
+struct rsc_mlpnp {
+    rsc_context* ctx = nullptr;
+    MLState st;
+    float fx = 0, fy = 0, cx = 0, cy = 0;
+    float4* d_pts = nullptr;
+    float2* d_uv = nullptr;
+    float2* d_brg = nullptr;
+    double* d_cov = nullptr;  // [N][9] when covariances were set
+    bool use_cov = false;
+    uint64_t* d_best = nullptr;
+    int words = 0;
+    int spec_out0 = -1, spec_H = 0;
+    rsc_stream* stream = nullptr;
+    RngStream own_rng;
+    ~rsc_mlpnp() {
+        for (void* p : {(void*)d_pts, (void*)d_uv, (void*)d_brg, (void*)d_cov, (void*)d_best})
+            if (p) (void)hipFree(p);
+    }
+};
+
+struct rsc_mpview {
+    rsc_context* ctx = nullptr;
+    int n = 0;
+    DevBuf<char> mem;  // state | pos | normal | dmax | dmin | desc
+    DevKfpPoints dev;  // device pointers
+};
+
+struct rsc_bow {
+    rsc_context* ctx = nullptr;
+    int n = 0;
+    int n_nodes = 0;
+    int n_feat = 0;
+    DevBuf<char> mem;            // desc | desc_fv | angle | node_id | node_begin | feat
+    size_t off_feat = 0;
+    std::vector<uint32_t> feat;  // host copy of the FeatureVector entries (validity flags re-applied)
+    DevBow hdr;                  // device pointers of this view (copied into every BowPair)
+};
+
+struct rsc_voc {
+    rsc_context* ctx = nullptr;
+    DevBuf<char> mem;        // desc | rec | orig | word | weight, all in breadth-first order
+    DevVoc dev{};
+    uint32_t n_words = 0;
+    int L = 0;
+    int lds_levels = 0;      // whole tree levels staged in LDS
+    int min_leaf_depth = 0;  // the shallowest childless node
+    int max_children = 0;
+    DevBuf<char> d_work;     // job table | descriptors | per-view outputs
+    PinBuf<char> h_work;
+    hipEvent_t ev[3] = {};
+    double last_ms[2] = {0, 0};
+    ~rsc_voc() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+struct rsc_kfdb {
+    rsc_context* ctx = nullptr;
+    int cap = 0, max_words = 0;
+    int hw = 0;  // slots in use: 1 + the highest slot ever added or referenced (queries sweep [0, hw))
+    uint32_t vocab = 0;
+    uint32_t next_seq = 1;
+    std::vector<uint8_t> present;
+    PinBuf<int32_t> covis_h, covis_n_h;  // host mirror of the covisibility table (pinned: the copy kernel reads it)
+    DevBuf<uint32_t> ids, seq;
+    DevBuf<double> vals;
+    DevBuf<char> qbuf;  // the query BowVector: ids | vals (8-aligned), one upload per query
+    DevBuf<int32_t> len, covis, covis_n, words, list, scored, best, tmp, counters, out;
+    DevBuf<unsigned long long> query, key;
+    DevBuf<float> score, sc, acc, tscore;
+    DevBuf<uint8_t> conn;
+    PinBuf<char> stage;  // query upload | candidates download
+    void touch(int s) { hw = std::max(hw, s + 1); }
+    DevKFDB dev() const {
+        DevKFDB d;
+        d.cap = hw;  // the kernels' sweep bound; the arrays are sized (and strided) by cap
+        d.max_words = max_words;
+        d.vocab = vocab;
+        d.ids = ids.p;
+        d.vals = vals.p;
+        d.len = len.p;
+        d.seq = seq.p;
+        d.covis = covis.p;
+        d.covis_n = covis_n.p;
+        for (int t = 0; t < 2; ++t) {
+            d.query[t] = query.p + (size_t)t * cap;
+            d.words[t] = words.p + (size_t)t * cap;
+            d.score[t] = score.p + (size_t)t * cap;
+        }
+        d.tscore = tscore.p;
+        d.list = list.p;
+        d.key = key.p;
+        d.scored = scored.p;
+        d.sc = sc.p;
+        d.acc = acc.p;
+        d.best = best.p;
+        d.tmp = tmp.p;
+        d.counters = counters.p;
+        d.out = out.p;
+        d.qids = reinterpret_cast<const uint32_t*>(qbuf.p);
+        d.qvals = reinterpret_cast<const double*>(qbuf.p);  // set per query (after the ids)
+        d.conn = conn.p;
+        return d;
+    }
+};
+
+// the validity flags of a FeatureVector's host copy (rsc_bow::feat), re-applied (rsc_views.cpp; exported like the next)
+extern "C" void flag_invalid(std::vector<uint32_t>& feat, const uint8_t* valid);
 // what rsc_search_by_projection_last_many refuses before any launch (an exported name since it exists)
 extern "C" int last_check_args(rsc_context* C, rsc_frameview* const* frames, rsc_lastframe* const* lasts, int count,
                                float th);
@@ -294,4 +413,91 @@ extern "C" int tri_search_impl(rsc_context* C, const rsc_bow* const* bow1, rsc_k
                     rsc_kfview* const* kf2, int count, const float* F12, const uint8_t* const* has_mp1,
                     const uint8_t* const* has_mp2, const int32_t* only_stereo, int check_orientation, int speculative,
                     int32_t* const* matches12, int32_t* nmatches, int32_t* den_zero, uint8_t* const* den_zero_slot);
+
+constexpr int kFaultWord = 4;  // rsc_context::h_flag[4]: the split eigen stage's fault word
+
+// The eigen stage's fault word (h_flag[kFaultWord], set by split_wait when a hand-off gives up):
+// read after the round's wait, cleared, and returned as an error instead of the round's results.
+inline int take_fault(rsc_context* C) {
+    if (__atomic_load_n(C->h_flag + kFaultWord, __ATOMIC_ACQUIRE) == 0) return 0;
+    __atomic_store_n(C->h_flag + kFaultWord, 0u, __ATOMIC_RELEASE);
+    g_last_error = "a device hand-off wait timed out (split_wait: eigen stage chase / row wave, or a streamed "
+                   "PoseOptimization pass, or an OptimizeSim3 chunk of the cooperative form); results discarded";
+    return RSC_ERR_INTERNAL;
+}
+
+inline void timing_begin(rsc_context* C, int slot) {
+    if (C->timing) (void)hipEventRecord(C->ev[slot], C->stream);
+}
+
+// The timed launch of the batched entry points: ev[3] and ev[4] around it, read by timing_read after
+// the call's synchronise.
+template <class Launch>
+inline hipError_t timed_launch(rsc_context* C, Launch&& launch) {
+    timing_begin(C, 3);
+    const hipError_t e = launch();
+    if (e == hipSuccess) timing_begin(C, 4);
+    return e;
+}
+
+// rsc_context_last_kernel_timing: [2] the launch; with `mid` (the launch recorded ev[5] between its two
+// kernels) also [0] setup kernel, [1] rounds kernel
+inline void timing_read(rsc_context* C, bool mid = false) {
+    if (!C->timing) return;
+    float ms[3] = {0, 0, 0};
+    (void)hipEventElapsedTime(&ms[2], C->ev[3], C->ev[4]);
+    if (mid) {
+        (void)hipEventElapsedTime(&ms[0], C->ev[3], C->ev[5]);
+        (void)hipEventElapsedTime(&ms[1], C->ev[5], C->ev[4]);
+    }
+    for (int i = mid ? 0 : 2; i < 3; ++i) C->last_ms[i] = ms[i];
+}
+
+// One batched call over a staging arena (rsc_arena.h): fill(h, d) writes the problem table and the
+// inputs into the pinned mirror h (d: the device addresses the table points at) and may refuse the call
+// with a status; launch(d) enqueues the kernels.  `download` false: nothing comes back; `mid`: see
+// timing_read.  Returns with the outputs in the mirror, [A.back, A.bytes).
+template <class Fill, class Launch>
+inline int arena_run(rsc_context* C, DevBuf<char>& dev, PinBuf<char>& pin, const Arena& A, Fill&& fill, Launch&& launch,
+              bool download = true, bool mid = false) {
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = dev.ensure(A.bytes)) return e;
+    if (int e = pin.ensure(A.bytes)) return e;
+    // the previous call's copies into and out of the pinned mirror must be complete before it is rewritten
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    char* h = pin.p;
+    char* d = dev.p;
+    if (int e = fill(h, d)) return e;
+    RSC_HIP(hipMemcpyAsync(d, h, A.up, hipMemcpyHostToDevice, C->stream));
+    RSC_HIP(timed_launch(C, [&] { return launch(d); }));
+    if (download) RSC_HIP(hipMemcpyAsync(h + A.back, d + A.back, A.bytes - A.back, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    timing_read(C, mid);
+    return 0;
+}
+
+// A view image (rsc_viewimage.h) into `mem` with one blocking copy; the pointer fields the builder named are
+// bound to the allocation first (they must still be alive: members of the view, or locals of the builder).
+// `wait`: work enqueued on the context stream may read what `mem` held before.  `hdr`: the view's header
+// struct, copied into its piece `hdr_at` of the image once its pointers are bound.
+template <class H = char>
+inline int upload_image(rsc_context* C, DevBuf<char>& mem, ViewImage& img, bool wait = false,
+                        Piece<H> hdr_at = {0}, const H* hdr = nullptr) {
+    RSC_HIP(hipSetDevice(C->device));
+    if (int e = mem.ensure(img.finish())) return e;
+    img.bind(mem.p);
+    if (hdr) std::memcpy(at(img.h.data(), hdr_at), hdr, sizeof(H));
+    if (wait) RSC_HIP(hipStreamSynchronize(C->stream));
+    RSC_HIP(hipMemcpy(mem.p, img.h.data(), img.h.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// rsc_*_destroy of everything that lives on a context: work already enqueued on its stream may still read it
+template <class V>
+inline void destroy_on_stream(V* v) {
+    if (!v) return;
+    (void)hipStreamSynchronize(v->ctx->stream);
+    delete v;
+}
+
 #pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // TEST-ONLY host program: the staging-arena cursor (rsc_arena.h) against the offset arithmetic the six
-// batched matchers of rsc_api.cpp carried before they shared it.  Each layout is built twice for a few
+// batched matchers (now in rsc_matchers.cpp) carried before they shared it.  Each layout is built twice for a few
 // tiny shapes: `was_*` restates the former three loops (own `al`, own running `off`), `now_*` takes the
 // same pieces from an Arena in the order the entry point takes them.  Every offset, up, back and bytes must
 // agree; two shapes are also checked against numbers worked out by hand.  Then, per layout:

@@ -2,7 +2,7 @@
 through the exits of g2o's Levenberg-Marquardt loop that rsc/synth.py's frustum scenes never reach
 (an LDLT that is not positive, non-finite chi2, NaN rho, no active edge), and through the sizes where
 the kernels change path (the 256-edge slab of poseopt.hip, the 64-edge chunk and 192-edge slab of
-sim3opt.hip, the 8192 limits of rsc_api.cpp).  Shared by tests/test_cpu_lm_edges.py (oracle == host
+sim3opt.hip, the 8192 limits of rsc_optim.cpp).  Shared by tests/test_cpu_lm_edges.py (oracle == host
 build, branch record) and tests/test_gpu_lm_edges.py (device == oracle).
 
 Every case is a rsc.synth frame / problem with fields edited; nothing here is an output of the oracle.
