@@ -11,7 +11,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
-     facade_lastproj_test facade_triang_test arena_test viewimage_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test
+     facade_lastproj_test facade_triang_test arena_test viewimage_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test ref_dbow2
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -125,6 +125,10 @@ $(LIBDIR)/seed_window_test_san: $(SEED_WINDOW_DEPS)
 oracle:
 	$(MAKE) -s -C oracle
 
+# TEST-ONLY: the reference's own DBoW2 around our driver (oracle/Makefile `ref`), where a reference tree exists
+ref_dbow2:
+	$(MAKE) -s -C oracle ref
+
 hostemu:
 	$(MAKE) -s -C tests/hostemu
 
@@ -150,8 +154,8 @@ fusekf_emu:
 	$(MAKE) -s -C tests/fusekf_emu
 
 clean:
-	rm -rf $(LIBDIR) oracle/build tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
+	rm -rf $(LIBDIR) oracle/build oracle/_ref tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
 	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build
 
-.PHONY: all oracle hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
+.PHONY: all oracle ref_dbow2 hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
         facade_voc_test chase_mirror_test arena_test viewimage_test rounds_test seed_window_test clean

@@ -10,9 +10,12 @@
 // (DBoW2::BowVector, DBoW2::FeatureVector).
 //
 // Loader: the reference's `while(!f.eof())` (:1378) turns the file's trailing newline into one more
-// child of the root with an uninitialised descriptor and weight 0 (Q in DESIGN.md); this loader
-// skips empty lines, so that node does not exist here.  A caller that wants to model it appends the
-// node to Nodes (parent 0, is_leaf 0, weight 0, a descriptor of its choice) and calls upload().
+// node whose parent and nIsLeaf are uninitialised reads (Q21 in DESIGN.md).  As built with gcc it is
+// one more child of the last line's parent and a WORD of weight 0 with an unwritten descriptor; this
+// loader skips empty lines, so that node does not exist here and size() is ONE LESS than the
+// reference's for such a file (the missing word has weight 0: no feature can score with it).  A
+// caller that wants to model it appends the node to Nodes (the last line's parent, is_leaf 1, weight
+// 0, a descriptor of its choice) and calls upload().
 // Only TF_IDF weighting with L1_NORM scoring (what ORBvoc.txt declares) is supported.
 // One mutex serialises transform(): Tracking and LocalMapping share the vocabulary.  In the reference tree:
 //     mpVocabulary = new rsc_orb::ORBVocabulary();  mpVocabulary->loadFromTextFile(strVocFile);

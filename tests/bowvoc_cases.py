@@ -4,6 +4,7 @@ import copy
 
 import numpy as np
 
+import ref_dbow2_io
 from rsc import synth
 
 
@@ -53,25 +54,67 @@ def depths(voc):
     return d
 
 
-def with_loader_quirk(voc):
-    """The reference loader's trailing-newline node: one more child of the root, not a word, weight
-    0, here with a chosen descriptor (the reference's is uninitialised memory)."""
+def with_loader_quirk(voc, observed=False):
+    """The reference loader's trailing-newline node, whose parent and nIsLeaf are
+    uninitialised reads.  observed=False: the shape C++11's "0 on failure" would give if the
+    extraction were attempted: one more child of the root, not a word, weight 0, here with a chosen
+    descriptor.  observed=True: what the built reference does (tests/golden/ref_dbow2.npz): the
+    previous line's values are reused, so it is one more child of the LAST LINE'S PARENT and a WORD
+    of weight 0; its descriptor is never written (32 zero bytes under the stand-in Mat::create)."""
     v = copy.deepcopy(voc)
-    rng = np.random.default_rng(7003)
-    extra = rng.integers(0, 256, size=(1, 32), dtype=np.uint8)
-    v.parent = np.concatenate([v.parent, np.zeros(1, np.int32)])
-    v.is_leaf = np.concatenate([v.is_leaf, np.zeros(1, np.uint8)])
+    if observed:
+        extra = np.zeros((1, 32), np.uint8)
+        parent, leaf = v.parent[-1:], v.is_leaf[-1:]
+    else:
+        extra = np.random.default_rng(7003).integers(0, 256, size=(1, 32), dtype=np.uint8)
+        parent, leaf = np.zeros(1, np.int32), np.zeros(1, np.uint8)
+    v.parent = np.concatenate([v.parent, parent.astype(np.int32)])
+    v.is_leaf = np.concatenate([v.is_leaf, leaf.astype(np.uint8)])
     v.desc = np.concatenate([v.desc, extra])
     v.weight = np.concatenate([v.weight, np.zeros(1)])
     return v, extra[0]
 
 
+def q21_vocabulary():
+    """k = 3, L = 2 with a sparse node 3 (8 bits set) whose children are >= 24 bits away from it: a
+    feature equal to node 3's descriptor is nearer to 32 zero bytes than to any child of node 3."""
+    voc = synth.make_vocabulary(np.random.default_rng(15), 3, 2)
+    assert voc.n_nodes == 13 and voc.parent[-1] == 3
+    rng = np.random.default_rng(7021)
+    voc.desc[3] = 0
+    voc.desc[3, :8] = 1
+    for c in (10, 11, 12):
+        assert voc.parent[c] == 3
+        m = np.zeros(256, np.uint8)
+        m[rng.choice(256, size=24 + 4 * (c - 10), replace=False)] = 1
+        voc.desc[c] = voc.desc[3] ^ np.packbits(m)
+    return voc
+
+
+def q21_descriptors(voc):
+    """90 descriptors for q21_vocabulary(); every third one is node 3's descriptor, half of those one
+    bit away -> (descriptors, indices of those features)."""
+    desc = synth.sample_descriptors(np.random.default_rng(150), voc, 90, mean_flips=5.0, random_frac=0.0)
+    hit = np.arange(0, 90, 3)
+    desc[hit] = voc.desc[3]
+    desc[hit[::2], 31] ^= 0x80
+    return desc, hit
+
+
+def fixture_vocabulary(z, name):
+    """Vocabulary `name` of tests/golden/ref_dbow2.npz as the built reference holds it after loading
+    its text file: the nodes of the file, and for a file with a trailing newline the extra word in the
+    shape the reference gave it (recorded in the fixture: its node id, parent and weight)."""
+    voc = synth.Vocabulary(int(z[f"voc.{name}.k"]), int(z[f"voc.{name}.L"]), 0, 0, z[f"voc.{name}.parent"].copy(),
+                           z[f"voc.{name}.is_leaf"].copy(), z[f"voc.{name}.desc"].copy(), z[f"voc.{name}.weight"].copy())
+    if bool(z[f"voc.{name}.newline"]):
+        last = z[f"voc.{name}.chain"][-1]
+        quirk, _ = with_loader_quirk(voc, observed=True)
+        assert last[0] == voc.n_nodes and last[1] == quirk.parent[-1] and z[f"voc.{name}.wweight_tail"].tolist() == [0.0]
+        return quirk
+    return voc
+
+
 def write_text_vocabulary(voc, path, trailing_newline=True):
-    """The ORBvoc.txt format: `k L scoring weighting`, then `parent isLeaf b0 .. b31 weight` per node
-    (the root has no line).  Weights are written with repr(), which round-trips a double."""
-    lines = [f"{voc.k} {voc.L} {voc.scoring} {voc.weighting}"]
-    for i in range(1, voc.n_nodes):
-        lines.append(f"{int(voc.parent[i])} {int(voc.is_leaf[i])} " + " ".join(str(int(b)) for b in voc.desc[i]) +
-                     f" {float(voc.weight[i])!r}")
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + ("\n" if trailing_newline else ""))
+    """The ORBvoc.txt format, through its one writer (tests/ref_dbow2_io.py)."""
+    ref_dbow2_io.write_vocabulary(path, voc.k, voc.L, voc.parent, voc.is_leaf, voc.desc, voc.weight, trailing_newline)

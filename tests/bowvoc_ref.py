@@ -16,6 +16,15 @@ def _distance(a: int, b: int) -> int:
     return bin(a ^ b).count("1")
 
 
+def normalize_l1(values):
+    """BowVector::normalize(L1) (BowVector.cpp:62-84) on the values in key order -> (norm, values):
+    one sum of fabs in std::map order, then one division each, and none when the norm is not > 0."""
+    norm = 0.0
+    for x in values:
+        norm += abs(x)
+    return norm, ([x / norm for x in values] if norm > 0.0 else list(values))
+
+
 class RefVocabulary:
     def __init__(self, voc):
         self.L = int(voc.L)
@@ -79,12 +88,9 @@ class RefVocabulary:
             else:
                 f_stop[i] = 1
         keys = sorted(v)
-        norm = 0.0
-        for k in keys:  # normalize(L1), std::map order
-            norm += abs(v[k])
-        if norm > 0.0 and normalize:
-            for k in keys:
-                v[k] /= norm
+        norm, normed = normalize_l1([v[k] for k in keys])
+        if normalize:
+            v = dict(zip(keys, normed))
         nodes = sorted(fv)
         begin = np.zeros(len(nodes) + 1, np.int32)
         feat = []

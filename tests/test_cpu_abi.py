@@ -49,3 +49,7 @@ def test_oracle_not_linked_into_product():
     import subprocess
     out = subprocess.run(["nm", "-D", engine.LIB_PATH], capture_output=True, text=True).stdout
     assert "ora_" not in out and "rsc_oracle" not in out
+    # nor anything of the reference's DBoW2 / DUtils (built only into oracle/_ref/ref_dbow2, oracle/Makefile)
+    full = subprocess.run(["nm", engine.LIB_PATH], capture_output=True, text=True).stdout
+    for text in (out, full):
+        assert "DBoW2" not in text and "DUtils" not in text

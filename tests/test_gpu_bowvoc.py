@@ -124,6 +124,24 @@ def test_loader_quirk_shape():
     assert voc.n_nodes - 1 not in got["node_id"]
 
 
+def test_loader_quirk_observed_shape():
+    """The trailing-newline node as the built reference makes it (DESIGN.md Q21,
+    tests/golden/ref_dbow2.npz): one more WORD of weight 0 under the last line's parent, its
+    descriptor 32 zero bytes.  The features nearest to it are stopped; without it they are filed."""
+    base = bc.q21_vocabulary()
+    voc, extra = bc.with_loader_quirk(base, observed=True)
+    assert voc.n_nodes == 14 and voc.parent[-1] == 3 and voc.is_leaf[-1] == 1 and not extra.any()
+    desc, hit = bc.q21_descriptors(base)
+    g, r = engine.Vocabulary(ctx(), voc), RefVocabulary(voc)
+    assert g.size == r.size() == 10
+    got, ref = check(g, r, desc, 1)
+    assert ref["f_stopped"][hit].all() and (ref["f_node"][hit] == 3).all() and (ref["f_word"][hit] == 9).all()
+    assert not np.isin(hit, got["feat"]).any() and len(got["feat"]) == 60
+    g0, r0 = engine.Vocabulary(ctx(), base), RefVocabulary(base)
+    got, ref = check(g0, r0, desc, 1)
+    assert g0.size == 9 and np.isin(hit, got["feat"]).all() and len(got["feat"]) == 90
+
+
 def test_ties_go_to_the_first_child():
     voc = synth.make_vocabulary(np.random.default_rng(16), 4, 3, duplicate_frac=0.5)
     g, r = engine.Vocabulary(ctx(), voc), RefVocabulary(voc)
