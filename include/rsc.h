@@ -1006,8 +1006,9 @@ int rsc_triangulate_pairs_many(rsc_context* ctx, rsc_kfview* const* kf1, rsc_kfv
  * and one triangulation launch from the initial slot state (mp_state != 0), then the neighbour order is
  * replayed on the host.  Outputs per current KeyFrame, indexed by its slot i1 (a slot is filled at most
  * once): new_neighbour[c][i1] = index into c's neighbour list or -1, new_idx2[c][i1], new_pos[c][i1][3],
- * nnew[c].  The reference's creation order is (neighbour, i1) ascending.  MapPoint allocation,
- * AddObservation / AddMapPoint, ComputeDistinctiveDescriptors and UpdateNormalAndDepth stay with the caller. */
+ * nnew[c].  The reference's creation order is (neighbour, i1) ascending.  MapPoint allocation and
+ * AddObservation / AddMapPoint stay with the caller; ComputeDistinctiveDescriptors and UpdateNormalAndDepth of
+ * the new points (:418-420) are one rsc_update_map_points_many call. */
 int rsc_create_new_map_points_many(rsc_context* ctx, const rsc_bow* const* bow_cur, rsc_kfview* const* kf_cur,
                                    int count, const int32_t* neigh_begin, const rsc_bow* const* bow_neigh,
                                    rsc_kfview* const* kf_neigh, int32_t* const* new_neighbour,
@@ -1030,6 +1031,63 @@ int rsc_create_new_map_points_many(rsc_context* ctx, const rsc_bow* const* bow_c
  * lists are RSC_OK. */
 int rsc_fuse_kf_many(rsc_context* ctx, rsc_kfview* const* kfs, rsc_mpview* const* points, int count,
                      const uint8_t* const* skip, float th, int32_t* const* best_idx, int32_t* nfused);
+
+/* ---- MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth in a batch ---------------
+ * The pair of calls the reference runs on every MapPoint a mapping step touched (src/MapPoint.cpp:224-289,
+ * :312-353; LocalMapping.cpp:147-148, :418-420, :493-506), for n_points points in one launch per size class.
+ * Each point has an ordered observation list, the caller's iteration of mObservations; the KeyFrames are
+ * rsc_kfview handles (descriptors, octaves and scale factors are resident there; the camera centre is the Ow
+ * of rsc_kfview_set_triangulation).
+ * what & 1, ComputeDistinctiveDescriptors: observations of a KeyFrame with kf_bad are dropped; of the N kept
+ * descriptors the one whose row of Hamming distances (the zero of the diagonal included) has the smallest
+ * lower median, the element of rank (int)(0.5 * (N - 1)), wins; ties go to the first in list order.  best_obs
+ * is its position in the point's list, -1 when N == 0 (every KeyFrame bad: no descriptor is written).
+ * what & 2, UpdateNormalAndDepth: every observation counts, bad KeyFrames included; normal = (sum over the list,
+ * in order, of (pos - Ow_i) / |pos - Ow_i|) / n, dmax = |pos - Ow_ref| * scale_ref[octave_ref[ref_idx]], dmin =
+ * dmax / scale_ref[n_levels - 1], every step rounded to float, IEEE divisions.  A point on a camera centre
+ * yields NaN, as in the reference.  When the reference KeyFrame is not among the observations the reference
+ * reads index 0 (std::map::operator[] on its copy): pass ref_idx = 0.
+ * A point with skip set (mbBad) or an empty list is left untouched: its entries of `out` keep what the caller
+ * put there, as does every entry of a field the call did not write for a point (desc when best_obs is -1;
+ * desc and best_obs without what & 1; normal, dmax, dmin without what & 2).  updated is written for every point.
+ * dst / dst_index (both may be NULL): dst_index[p] is the slot of point p in the resident view dst, or -1;
+ * every field written for p is also stored into that slot on the device, other fields and slots keep their
+ * bytes, so the matchers can read the view without a host round trip.
+ * A limit the reference does not have: a list holds at most RSC_MPUPDATE_MAX_OBS observations.
+ * RSC_ERR_ARG before any launch, outputs untouched: what outside 1..3, obs_begin not ascending, a list longer
+ * than the limit, obs_kf / obs_idx / ref_kf / ref_idx / dst_index out of range, two points with one dst slot,
+ * dst of another context, with what & 2 a referenced view without rsc_kfview_set_triangulation or
+ * octave[ref_idx] outside [0, n_levels).  The lists of skipped points are not read.  n_points == 0 and
+ * all-empty lists are RSC_OK.  Parity with an Eigen build of the reference is unpinned (as for the
+ * triangulation); the arithmetic is the one stated above. */
+#define RSC_MPUPDATE_MAX_OBS 1024
+typedef struct {
+    int32_t n_points;
+    const uint8_t* skip;        /* [n_points] mbBad: the point is left untouched (NULL: none) */
+    const float*   pos;         /* [n_points][3] mWorldPos */
+    const int32_t* obs_begin;   /* [n_points + 1] CSR over the observations, in mObservations order */
+    const int32_t* obs_kf;      /* [n_obs] index into kfs[] */
+    const int32_t* obs_idx;     /* [n_obs] mit->second */
+    const uint8_t* kf_bad;      /* [n_kfs] pKF->isBad() (NULL: none) */
+    const int32_t* ref_kf;      /* [n_points] mpRefKF as an index into kfs[] */
+    const int32_t* ref_idx;     /* [n_points] observations[pRefKF] */
+} rsc_mappoint_updates;
+
+typedef struct {
+    uint8_t* desc;        /* [n_points][32] */
+    int32_t* best_obs;    /* [n_points] position of BestIdx in the point's list, -1: descriptor not written */
+    float*   normal;      /* [n_points][3] */
+    float*   dmax, *dmin; /* [n_points] */
+    uint8_t* updated;     /* [n_points] bit 0 descriptor written, bit 1 normal / depth written */
+} rsc_mappoint_update_out;   /* any member may be NULL */
+
+int rsc_update_map_points_many(rsc_context* ctx, rsc_kfview* const* kfs, int n_kfs,
+                               const rsc_mappoint_updates* in, int what /* 1 descriptor | 2 normal+depth */,
+                               const rsc_mappoint_update_out* out, rsc_mpview* dst, const int32_t* dst_index);
+/* Diagnostic: a resident MapPoint view read back (after the work enqueued on its context); any array may be
+ * NULL.  state [n], pos / normal [n][3], dmax / dmin [n], desc [n][32]. */
+int rsc_mpview_download(rsc_mpview* view, uint8_t* state, float* pos, float* normal, float* dmax, float* dmin,
+                        uint8_t* desc);
 
 /* Diagnostics below: `cap` = number of uint64 slots at `out`; RSC_ERR_ARG when it is smaller than
  * the layout (64*24, 64*8, 4096*4 and at most 64*96 words).

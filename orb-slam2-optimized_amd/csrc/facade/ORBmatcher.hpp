@@ -209,6 +209,24 @@ KFViewUpload upload_kfview(const KFPtr& pKF, const std::vector<MPPtr>& mps) {
     return u;
 }
 
+// One upload per distinct KeyFrame object of a list; ki[c] = the view of vpKFs[c] (shared by the matchers and by
+// MapPoint.hpp).
+template <class KFPtr>
+void upload_distinct(const std::vector<KFPtr>& vpKFs, std::vector<KFViewUpload>& views, std::vector<int>& ki) {
+    std::vector<const void*> keys;
+    ki.assign(vpKFs.size(), 0);
+    for (size_t c = 0; c < vpKFs.size(); ++c) {
+        size_t j = 0;
+        for (; j < keys.size(); ++j)
+            if (keys[j] == (const void*)&*vpKFs[c]) break;
+        if (j == keys.size()) {
+            keys.push_back((const void*)&*vpKFs[c]);
+            views.push_back(upload_kfview(vpKFs[c], vpKFs[c]->GetMapPointMatches()));
+        }
+        ki[c] = (int)j;
+    }
+}
+
 // Customization point: Twc as KeyFrame::SetPose stored it (KeyFrame.cpp:64-66), an object with rotation() /
 // translation() (Eigen::Isometry3f).
 template <class KF>
@@ -929,6 +947,8 @@ public:
     //     whose list position is behind the loop (and a repeated pointer to it is in pKF from now on), or
     //     pMPinKF, which is in pKF and skipped by :695 for the rest of the call.
     // The KeyFrames read nothing that Fuse changes (keypoints, pose, grid), so their views are uploaded once.
+    // The step that follows both directions, ComputeDistinctiveDescriptors and UpdateNormalAndDepth on the current
+    // KeyFrame's points (:493-506), is rsc_orb::UpdateMapPointsOf(pKF) of MapPoint.hpp.
     template <class KFPtr, class MPPtr>
     std::vector<int> FuseMany(const std::vector<KFPtr>& vpTargetKFs, const std::vector<MPPtr>& vpMapPoints,
                               float th = 3.0f) {
@@ -1140,18 +1160,7 @@ private:
     template <class KFPtr>
     static void upload_distinct(const std::vector<KFPtr>& vpKFs, std::vector<detail::KFViewUpload>& views,
                                 std::vector<int>& ki) {
-        std::vector<const void*> keys;
-        ki.assign(vpKFs.size(), 0);
-        for (size_t c = 0; c < vpKFs.size(); ++c) {
-            size_t j = 0;
-            for (; j < keys.size(); ++j)
-                if (keys[j] == (const void*)&*vpKFs[c]) break;
-            if (j == keys.size()) {
-                keys.push_back((const void*)&*vpKFs[c]);
-                views.push_back(detail::upload_kfview(vpKFs[c], vpKFs[c]->GetMapPointMatches()));
-            }
-            ki[c] = (int)j;
-        }
+        detail::upload_distinct(vpKFs, views, ki);
     }
 
     // rsc_fuse_kf_many for KeyFrames c0 .. against the points of `view` (pts: its MapPoints), skip as it is now.

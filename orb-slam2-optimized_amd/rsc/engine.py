@@ -65,6 +65,7 @@ EXPORTED = [
     "rsc_track_motion_model_many",
     "rsc_kfview_set_triangulation", "rsc_search_for_triangulation_many", "rsc_triangulate_pairs_many",
     "rsc_create_new_map_points_many", "rsc_fuse_kf_many",
+    "rsc_update_map_points_many", "rsc_mpview_download",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -371,6 +372,20 @@ class MPView:
         _check(load_library().rsc_mpview_create(ctx.h, C.byref(m), C.byref(h)), "rsc_mpview_create")
         self.h = h
 
+    def download(self):
+        """The view as it is in HBM now (rsc_mpview_download, a diagnostic): a namespace with n, state, pos, normal,
+        dmax, dmin, desc."""
+        import types
+        n = max(self.n, 1)
+        o = types.SimpleNamespace(n=self.n, state=np.zeros(n, np.uint8), pos=np.zeros((n, 3), np.float32),
+                                  normal=np.zeros((n, 3), np.float32), dmax=np.zeros(n, np.float32),
+                                  dmin=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8))
+        _check(load_library().rsc_mpview_download(self.h, o.state, o.pos, o.normal, o.dmax, o.dmin, o.desc),
+               "rsc_mpview_download")
+        for k in ("state", "pos", "normal", "dmax", "dmin", "desc"):
+            setattr(o, k, getattr(o, k)[:self.n])
+        return o
+
     def close(self):
         if getattr(self, "h", None):
             load_library().rsc_mpview_destroy(self.h)
@@ -629,6 +644,72 @@ def fuse_kf_many(ctx: Context, kfs, points, skip, th: float):
     _check(load_library().rsc_fuse_kf_many(ctx.h, _handles(kfs), _handles(points), c, _ptrs(sk), float(th),
                                            _ptrs(best), nf), "rsc_fuse_kf_many")
     return [b[:p.n] for b, p in zip(best, points)], nf[:c]
+
+
+class MapPointUpdates(C.Structure):
+    """rsc_mappoint_updates (include/rsc.h)."""
+    _fields_ = [("n_points", C.c_int32), ("skip", C.c_void_p), ("pos", C.c_void_p), ("obs_begin", C.c_void_p),
+                ("obs_kf", C.c_void_p), ("obs_idx", C.c_void_p), ("kf_bad", C.c_void_p), ("ref_kf", C.c_void_p),
+                ("ref_idx", C.c_void_p)]
+
+
+class MapPointUpdateOut(C.Structure):
+    """rsc_mappoint_update_out (include/rsc.h)."""
+    _fields_ = [("desc", C.c_void_p), ("best_obs", C.c_void_p), ("normal", C.c_void_p), ("dmax", C.c_void_p),
+                ("dmin", C.c_void_p), ("updated", C.c_void_p)]
+
+
+MPUPDATE_MAX_OBS = 1024  # RSC_MPUPDATE_MAX_OBS
+# what update_map_points_many puts into the entries the call does not write
+MPUPDATE_FILL = dict(desc=0xA5, best_obs=-7, normal=np.float32(-77.0), dmax=np.float32(-77.0), dmin=np.float32(-77.0))
+
+
+def update_map_points_many(ctx: Context, kfs, updates, what: int = 3, dst=None, dst_index=None, out=None):
+    """MapPoint::ComputeDistinctiveDescriptors (what & 1) and MapPoint::UpdateNormalAndDepth (what & 2)
+    (MapPoint.cpp:224-289, :312-353; rsc_update_map_points_many) for a batch of points over the KFViews `kfs`
+    (with set_triangulation for what & 2).  `updates`: an object with n_points, skip uint8 [n], pos float32 [n,3],
+    obs_begin int32 [n+1], obs_kf / obs_idx int32 [n_obs], kf_bad uint8 [len(kfs)] or None, ref_kf / ref_idx int32
+    [n].  dst / dst_index: an MPView and int32 [n] slots (-1: none) that receive the written fields on the device.
+    Returns a dict: desc uint8 [n,32], best_obs int32 [n], normal float32 [n,3], dmax, dmin float32 [n], updated
+    uint8 [n]; entries the call did not write hold MPUPDATE_FILL.  out: such a dict to write into instead (entries
+    not written keep what it holds, and a refused call leaves it as it is)."""
+    n = int(updates.n_points)
+    m = max(n, 1)
+    arr = lambda a, dt, k: (np.ascontiguousarray(a, dt).reshape(-1) if a is not None and np.size(a) else np.zeros(k, dt))
+    keep = dict(skip=arr(updates.skip, np.uint8, m), pos=arr(updates.pos, np.float32, 3 * m),
+                obs_begin=arr(updates.obs_begin if n else None, np.int32, m + 1), obs_kf=arr(updates.obs_kf, np.int32, 1),
+                obs_idx=arr(updates.obs_idx, np.int32, 1), ref_kf=arr(updates.ref_kf, np.int32, m),
+                ref_idx=arr(updates.ref_idx, np.int32, m))
+    assert keep["obs_begin"].size == m + 1 and keep["pos"].size == 3 * m and keep["skip"].size == m
+    u = MapPointUpdates()
+    u.n_points = n
+    for k, a in keep.items():
+        setattr(u, k, a.ctypes.data)
+    bad = getattr(updates, "kf_bad", None)
+    if bad is not None:
+        bad = arr(bad, np.uint8, 1)
+        assert bad.size >= len(kfs)
+        u.kf_bad = bad.ctypes.data
+    F = MPUPDATE_FILL
+    res = dict(desc=np.full((m, 32), F["desc"], np.uint8), best_obs=np.full(m, F["best_obs"], np.int32),
+               normal=np.full((m, 3), F["normal"], np.float32), dmax=np.full(m, F["dmax"], np.float32),
+               dmin=np.full(m, F["dmin"], np.float32), updated=np.full(m, 0xFF, np.uint8))
+    if out is not None:
+        assert all(out[k].dtype == a.dtype and out[k].size >= a[:n].size and out[k].flags.c_contiguous
+                   for k, a in res.items())
+        res = out
+    o = MapPointUpdateOut()
+    for k, a in res.items():
+        setattr(o, k, a.ctypes.data)
+    di = None
+    if dst is not None:
+        di = arr(dst_index, np.int32, m)
+        assert di.size == m
+    _check(load_library().rsc_update_map_points_many(ctx.h, _handles(kfs), len(kfs), C.byref(u), int(what),
+                                                      C.byref(o), dst.h if dst is not None else None,
+                                                      di.ctypes.data if di is not None else None),
+           "rsc_update_map_points_many")
+    return res if out is not None else {k: a[:n] for k, a in res.items()}
 
 
 def loop_verify_many(ctx: Context, kf_cur, kf_matched, loop_points, S, matches, already):
@@ -986,6 +1067,9 @@ def load_library(path: str = LIB_PATH):
                                      C.POINTER(C.c_void_p), i32p]
     L.rsc_fuse_kf_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(C.c_void_p), C.c_float,
                                    C.POINTER(C.c_void_p), i32p]
+    L.rsc_update_map_points_many.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(MapPointUpdates), C.c_int,
+                                             C.POINTER(MapPointUpdateOut), vp, C.c_void_p]
+    L.rsc_mpview_download.argtypes = [vp, u8p, f32p, f32p, f32p, f32p, u8p]
     L.rsc_loop_verify_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, f64p_,
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                        C.POINTER(LoopVerifyResult), C.POINTER(C.c_void_p)]
