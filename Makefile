@@ -12,7 +12,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
      facade_lastproj_test facade_triang_test arena_test viewimage_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test ref_dbow2 \
-     mpupdate_emu facade_mpupdate_test
+     mpupdate_emu facade_mpupdate_test stereo_emu facade_stereo_test
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -41,6 +41,13 @@ $(LIBDIR)/mpupdate.o: $(CSRC)/mpupdate.hip $(HDRS)
 		2> $(LIBDIR)/mpupdate.resources.txt || { cat $(LIBDIR)/mpupdate.resources.txt >&2; exit 1; }
 	@grep -v 'Rpass-analysis=kernel-resource-usage' $(LIBDIR)/mpupdate.resources.txt >&2 || true
 
+# stereo.hip likewise (the match and cut kernels of ComputeStereoMatches: DESIGN.md §2.16)
+$(LIBDIR)/stereo.o: $(CSRC)/stereo.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -fno-caret-diagnostics -c $< -o $@ \
+		2> $(LIBDIR)/stereo.resources.txt || { cat $(LIBDIR)/stereo.resources.txt >&2; exit 1; }
+	@grep -v 'Rpass-analysis=kernel-resource-usage' $(LIBDIR)/stereo.resources.txt >&2 || true
+
 $(LIBDIR)/librsc.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
@@ -54,7 +61,7 @@ $(LIBDIR)/librsc_spin1.so: $(OBJS:%/kernels.o=%/kernels_spin1.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 FACADE_TESTS = facade_test facade_proj_test facade_loopproj_test facade_localproj_test facade_lastproj_test \
-               facade_triang_test facade_fusekf_test facade_voc_test facade_mpupdate_test
+               facade_triang_test facade_fusekf_test facade_voc_test facade_mpupdate_test facade_stereo_test
 
 $(FACADE_TESTS): %: $(LIBDIR)/%
 
@@ -164,9 +171,13 @@ fusekf_emu:
 mpupdate_emu:
 	$(MAKE) -s -C tests/mpupdate_emu
 
+stereo_emu:
+	$(MAKE) -s -C tests/stereo_emu
+
 clean:
 	rm -rf $(LIBDIR) oracle/build oracle/_ref tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
-	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build tests/mpupdate_emu/build
+	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build tests/mpupdate_emu/build \
+	       tests/stereo_emu/build
 
-.PHONY: all oracle ref_dbow2 hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu mpupdate_emu facade_mpupdate_test facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
+.PHONY: all oracle ref_dbow2 hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu mpupdate_emu stereo_emu facade_stereo_test facade_mpupdate_test facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
         facade_voc_test chase_mirror_test arena_test viewimage_test rounds_test seed_window_test clean

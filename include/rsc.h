@@ -1089,6 +1089,49 @@ int rsc_update_map_points_many(rsc_context* ctx, rsc_kfview* const* kfs, int n_k
 int rsc_mpview_download(rsc_mpview* view, uint8_t* state, float* pos, float* normal, float* dmax, float* dmin,
                         uint8_t* desc);
 
+/* ---- Frame::ComputeStereoMatches: mvuRight and mvDepth of a resident Frame ----------------------------
+ * Frame::ComputeStereoMatches() (src/Frame.cpp:538-673, the keypoint-only matcher: no image is read) for c <
+ * count in one launch per phase.  The left side is the resident view frames[c] (kp = mvKeysUn, octave, desc,
+ * scale_factors of rsc_frame_features); right[c] carries mvKeysRight as extracted and mDescriptorsRight.
+ * With maxD = mbf / mb and r = 2 * scale[octaveL], left keypoint i (skipped when uL < 0) takes, among the right
+ * keypoints with yL - r < yR <= yL + r, octaveR in [octaveL - 1, octaveL + 1] and uL - maxD <= uR <= uL, the
+ * one with the smallest (descriptor distance, yR, index); -0.0f and +0.0f are one y.  It is accepted when the
+ * distance is below 75 and disparity = uL - uR lies in [0, maxD): mvuRight = uR, mvDepth = mbf / disparity,
+ * and for disparity == 0 mvuRight = (float)((double)uL - 0.01), mvDepth = mbf / (float)0.01.  The cut then
+ * resets to -1 / -1 every accepted keypoint with (float)distance >= th_dist = 1.5f * 1.4f * median, median =
+ * the element of rank size / 2 of the accepted distances (a median of 0 removes every match).  Every float
+ * operation is the reference's, rounded once.
+ * u_right[c] / depth[c] (frames[c] n entries): mvuRight / mvDepth.  best_right[c] / best_dist[c] (either may be
+ * NULL or hold NULL entries): the matched right index and distance before the cut, -1 where nothing was
+ * accepted (the reference does not keep them).  set_stereo != 0 leaves every view as
+ * rsc_frameview_set_stereo(frames[c], u_right[c], mbf[c]) would, without an upload.
+ * Pinned where the reference is undefined: without an accepted match nothing is removed, median = -1 and th_dist
+ * = 1.5f * 1.4f * -1; mb is an argument (the reference reads Frame::mb before its constructor assigns it).
+ * Limits the reference does not have: at most RSC_STEREO_MAX_RIGHT right keypoints; mbf and mb finite and > 0.
+ * RSC_ERR_ARG before any launch, outputs untouched: right[c].n above the limit, such an mbf or mb, a non-finite
+ * right keypoint coordinate (std::sort on NaN in the reference), a left octave outside [0, n_levels), the same
+ * view twice in one call with set_stereo, a view of another context.  Right octaves may be any int32.  count ==
+ * 0, a left frame with n == 0 and a right frame with n == 0 (every entry -1) are RSC_OK.  With timing enabled,
+ * rsc_context_last_kernel_timing gives [0] the match kernel, [1] the cut kernel, [2] both (ms). */
+#define RSC_STEREO_MAX_RIGHT 8192
+typedef struct {
+    int32_t n;              /* mvKeysRight.size(), <= RSC_STEREO_MAX_RIGHT */
+    const float* kp;        /* [n][2] mvKeysRight[i].pt, as extracted */
+    const int32_t* octave;  /* [n] */
+    const uint8_t* desc;    /* [n][32] mDescriptorsRight */
+} rsc_right_features;
+typedef struct {
+    int32_t n_candidates;   /* vDistIdx.size(): accepted before the cut */
+    int32_t n_removed;      /* reset to -1 by the cut */
+    int32_t median;         /* -1 when n_candidates == 0 */
+    float   th_dist;
+} rsc_stereo_result;
+int rsc_compute_stereo_matches_many(rsc_context* ctx, rsc_frameview* const* frames,
+                                    const rsc_right_features* right, int count, const float* mbf,
+                                    const float* mb, int set_stereo, float* const* u_right, float* const* depth,
+                                    int32_t* const* best_right, int32_t* const* best_dist,
+                                    rsc_stereo_result* result);
+
 /* Diagnostics below: `cap` = number of uint64 slots at `out`; RSC_ERR_ARG when it is smaller than
  * the layout (64*24, 64*8, 4096*4 and at most 64*96 words).
  * Diagnostic: wall-clock (100 MHz) phase stamps of the last PnP refine launch, [job < 64][24]:

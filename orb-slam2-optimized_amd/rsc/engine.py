@@ -66,6 +66,7 @@ EXPORTED = [
     "rsc_kfview_set_triangulation", "rsc_search_for_triangulation_many", "rsc_triangulate_pairs_many",
     "rsc_create_new_map_points_many", "rsc_fuse_kf_many",
     "rsc_update_map_points_many", "rsc_mpview_download",
+    "rsc_compute_stereo_matches_many",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -307,6 +308,12 @@ class FrameView:
         if not self.n:
             u = np.zeros(1, np.float32)
         _check(load_library().rsc_frameview_set_stereo(self.h, u, float(mbf)), "rsc_frameview_set_stereo")
+
+    def compute_stereo(self, right, mbf: float, mb: float, set_stereo: bool = True):
+        """Frame::ComputeStereoMatches of this Frame against the right image's features `right` (an object with
+        r_kp float32 [m,2], r_octave int32 [m], r_desc uint8 [m,32]); see compute_stereo_matches_many, whose
+        result dict for the one frame this returns."""
+        return compute_stereo_matches_many(self.ctx, [self], [right], [mbf], [mb], set_stereo)[0]
 
     def close(self):
         if getattr(self, "h", None):
@@ -712,6 +719,64 @@ def update_map_points_many(ctx: Context, kfs, updates, what: int = 3, dst=None, 
     return res if out is not None else {k: a[:n] for k, a in res.items()}
 
 
+class RightFeatures(C.Structure):
+    """rsc_right_features (include/rsc.h)."""
+    _fields_ = [("n", C.c_int32), ("kp", C.c_void_p), ("octave", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class StereoResult(C.Structure):
+    """rsc_stereo_result (include/rsc.h)."""
+    _fields_ = [("n_candidates", C.c_int32), ("n_removed", C.c_int32), ("median", C.c_int32), ("th_dist", C.c_float)]
+
+
+STEREO_MAX_RIGHT = 8192  # RSC_STEREO_MAX_RIGHT
+# what compute_stereo_matches_many puts into its outputs before the call (a refused call leaves them)
+STEREO_FILL = dict(u_right=np.float32(-77.0), depth=np.float32(-77.0), best_right=-7, best_dist=-7)
+
+
+def compute_stereo_matches_many(ctx: Context, frames, rights, mbf, mb, set_stereo: bool = True,
+                                diagnostics: bool = True, out=None):
+    """Frame::ComputeStereoMatches (Frame.cpp:538-673; rsc_compute_stereo_matches_many) for each (FrameView,
+    right features) pair in one launch per phase.  rights[c]: an object with r_kp float32 [m,2] (mvKeysRight pt, as
+    extracted), r_octave int32 [m], r_desc uint8 [m,32]; mbf / mb: one float per frame.  set_stereo leaves every
+    view as FrameView.set_stereo(u_right, mbf) would, without an upload.  Returns one dict per frame: u_right,
+    depth float32 [n] (mvuRight, mvDepth), best_right, best_dist int32 [n] (before the cut, -1: not accepted; None
+    without `diagnostics`), n_candidates, n_removed, median, th_dist.  out: a list of such dicts of arrays to write
+    into instead (a refused call leaves them as they are)."""
+    c = len(frames)
+    assert len(rights) == c
+    keep, R = [], (RightFeatures * max(c, 1))()
+    for k, r in enumerate(rights):
+        a = [np.ascontiguousarray(r.r_kp, np.float32).reshape(-1), np.ascontiguousarray(r.r_octave, np.int32).reshape(-1),
+             np.ascontiguousarray(r.r_desc, np.uint8).reshape(-1)]
+        assert a[0].size == 2 * a[1].size and a[2].size == 32 * a[1].size
+        R[k].n = a[1].size
+        a = [x if x.size else np.zeros(32, x.dtype) for x in a]
+        R[k].kp, R[k].octave, R[k].desc = (x.ctypes.data for x in a)
+        keep.append(a)
+    F = STEREO_FILL
+    if out is None:
+        out = [dict(u_right=np.full(max(f.n, 1), F["u_right"], np.float32), depth=np.full(max(f.n, 1), F["depth"], np.float32),
+                    best_right=np.full(max(f.n, 1), F["best_right"], np.int32) if diagnostics else None,
+                    best_dist=np.full(max(f.n, 1), F["best_dist"], np.int32) if diagnostics else None) for f in frames]
+    res = (StereoResult * max(c, 1))()
+    fm = np.ascontiguousarray(mbf, np.float32).reshape(-1) if c else np.zeros(1, np.float32)
+    fb = np.ascontiguousarray(mb, np.float32).reshape(-1) if c else np.zeros(1, np.float32)
+    assert fm.size == max(c, 1) and fb.size == max(c, 1)
+    diag = lambda k: (C.c_void_p * max(c, 1))(*[o[k].ctypes.data if o[k] is not None else None for o in out]) \
+        if diagnostics else None
+    _check(load_library().rsc_compute_stereo_matches_many(
+        ctx.h, _handles(frames), R, c, fm, fb, int(bool(set_stereo)), _ptrs([o["u_right"] for o in out]),
+        _ptrs([o["depth"] for o in out]), diag("best_right"), diag("best_dist"), res), "rsc_compute_stereo_matches_many")
+    ret = []
+    for f, o, r in zip(frames, out, res):
+        d = {k: (a[:f.n] if a is not None else None) for k, a in o.items() if k in F}
+        d.update(n_candidates=int(r.n_candidates), n_removed=int(r.n_removed), median=int(r.median),
+                 th_dist=np.float32(r.th_dist))
+        ret.append(d)
+    return ret
+
+
 def loop_verify_many(ctx: Context, kf_cur, kf_matched, loop_points, S, matches, already):
     """The closing stage of LoopClosing::ComputeSim3 (LoopClosing.cpp:318-320, :360-370;
     rsc_loop_verify_many) on the result of the gated loop events: S [count][8] = LoopGateResult.S,
@@ -1070,6 +1135,8 @@ def load_library(path: str = LIB_PATH):
     L.rsc_update_map_points_many.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(MapPointUpdates), C.c_int,
                                              C.POINTER(MapPointUpdateOut), vp, C.c_void_p]
     L.rsc_mpview_download.argtypes = [vp, u8p, f32p, f32p, f32p, f32p, u8p]
+    L.rsc_compute_stereo_matches_many.argtypes = [vp, C.POINTER(vp), C.POINTER(RightFeatures), C.c_int, f32p, f32p,
+                                                  C.c_int] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(StereoResult)]
     L.rsc_loop_verify_many.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, f64p_,
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                        C.POINTER(LoopVerifyResult), C.POINTER(C.c_void_p)]
