@@ -1166,6 +1166,13 @@ int rsc_diag_sim3opt_phases(rsc_context* ctx, uint64_t* out, int cap);
 int rsc_diag_kfdb_stamps(rsc_context* ctx, uint64_t* out, int cap);
 /* Diagnostic: wall-clock (100 MHz) phase stamps of the last SearchByBoW launch, [pair < 64][96]. */
 int rsc_diag_bow_phase_stamps(rsc_context* ctx, uint64_t* out, int cap);
+/* Diagnostic (tests of history independence): waits for the context stream, then fills every staging
+ * buffer of the batched calls with `byte` (0..255) over its whole capacity: the matcher arenas (the shared
+ * projection / Fuse / triangulation / MapPoint-update / stereo arena, SearchBySim3's, SearchByBoW's, and the
+ * work arena of every rsc_voc created on the context) and the PoseOptimization and OptimizeSim3 input and
+ * result buffers, each with its pinned mirror.  Resident views, KeyFrame databases and solvers are not
+ * touched.  Returns the number of bytes filled (device and pinned together), or a negative RSC_ERR_*. */
+int64_t rsc_diag_fill_staging(rsc_context* ctx, int byte);
 
 /* ---- glibc rand() helpers (Thirdparty/DBoW2/DUtils/Random.cpp:33-50) -------------------------- */
 /* First n rand() outputs after srand(seed), produced with the device jump table (parity hook). */

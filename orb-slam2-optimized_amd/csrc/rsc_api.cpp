@@ -1151,6 +1151,28 @@ int rsc_diag_round_paths(rsc_context* C, int64_t out[3]) {
     return RSC_OK;
 }
 
+int64_t rsc_diag_fill_staging(rsc_context* C, int byte) {
+    if (!C || byte < 0 || byte > 255) return RSC_ERR_ARG;
+    RSC_HIP(hipSetDevice(C->device));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    int64_t total = 0;
+    auto fill = [&](DevBuf<char>& d, PinBuf<char>& h) -> hipError_t {
+        if (h.p) std::memset(h.p, byte, h.cap);
+        total += (int64_t)h.cap + (int64_t)d.cap;
+        return d.p ? hipMemsetAsync(d.p, byte, d.cap, C->stream) : hipSuccess;
+    };
+    RSC_HIP(fill(C->d_fp, C->h_fp));
+    RSC_HIP(fill(C->d_s3m, C->h_s3m));
+    RSC_HIP(fill(C->d_bow, C->h_bow));
+    for (rsc_voc* V : C->vocs) RSC_HIP(fill(V->d_work, V->h_work));
+    RSC_HIP(fill(C->d_po_in, C->h_po_in));
+    RSC_HIP(fill(C->d_po_res, C->h_po_res));
+    RSC_HIP(fill(C->d_so_in, C->h_so_in));
+    RSC_HIP(fill(C->d_so_res, C->h_so_res));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    return total;
+}
+
 int rsc_context_set_sim3opt_helpers(rsc_context* C, int helpers) {
     if (!C || helpers < -1) return RSC_ERR_ARG;
     C->so_helpers = helpers;

@@ -147,6 +147,8 @@ struct rsc_context {
     // SearchByBoW: pair table + output vectors + match counts (device, pinned mirror)
     DevBuf<char> d_bow;
     PinBuf<char> h_bow;
+    // the vocabularies created on this context (rsc_diag_fill_staging reaches their work arenas)
+    std::vector<struct rsc_voc*> vocs;
     // SearchByProjection (Frame, KeyFrame): problem table + flags + per-MapPoint scratch + outputs
     DevBuf<char> d_fp;
     PinBuf<char> h_fp;

@@ -7,7 +7,13 @@
 namespace rsc {
 
 constexpr int kProjSub = 16;          // lanes that walk one window together
-constexpr int kProjWalkCap = 4096;    // LDS list of the points that walk their window this round (16 KB)
+// LDS list of the points that walk their window this round (16 KB).  A point whose slot lands at or past the cap
+// walks alone inside the pick loop (best() instead of best_coop()): the same decision, so the same fixed point.
+// Reached only when more than kProjWalkCap points of one problem have used up their cache in one round, e.g.
+// 4,200 identical points over 12 features within 1 px of their projection at distances 3 + 5 k: 4,197 walkers in
+// each of the last three of 6 rounds (tests/walk_list_cases.py, which reads the cap from this line; the cases at
+// cap, cap + 1 and cap + 101 run in tests/test_gpu_walk_list.py).
+constexpr int kProjWalkCap = 4096;
 constexpr unsigned long long kProjNoKey = ~0ull;
 
 // proj_walk by kSub lanes, as a fold.  For one column ix the cells iy0..iy1 are contiguous in the CSR (cell =

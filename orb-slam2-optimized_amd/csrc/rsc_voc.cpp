@@ -1,4 +1,5 @@
 // rsc_voc.cpp — the vocabulary of the C ABI: create, transform, and the BoW view built from a transform.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include "rsc_host.h"
@@ -91,11 +92,18 @@ int rsc_voc_create(rsc_context* C, const rsc_vocabulary_nodes* v, rsc_voc** out)
     V->dev.n_nodes = nn;
     V->dev.lds_nodes = lds_nodes;
     V->dev.max_depth = max_depth;
+    C->vocs.push_back(V.get());
     *out = V.release();
     return RSC_OK;
 }
 
-void rsc_voc_destroy(rsc_voc* V) { destroy_on_stream(V); }
+void rsc_voc_destroy(rsc_voc* V) {
+    if (V) {
+        auto& vs = V->ctx->vocs;
+        vs.erase(std::remove(vs.begin(), vs.end(), V), vs.end());
+    }
+    destroy_on_stream(V);
+}
 
 int rsc_voc_size(const rsc_voc* V, uint32_t* n_words) {
     if (!V || !n_words) return RSC_ERR_ARG;

@@ -67,6 +67,7 @@ EXPORTED = [
     "rsc_create_new_map_points_many", "rsc_fuse_kf_many",
     "rsc_update_map_points_many", "rsc_mpview_download",
     "rsc_compute_stereo_matches_many",
+    "rsc_diag_fill_staging",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -1005,6 +1006,8 @@ def load_library(path: str = LIB_PATH):
     L.rsc_context_set_eig_rows.argtypes = [vp, C.c_int]
     L.rsc_context_set_round_args.argtypes = [vp, C.c_int]
     L.rsc_diag_round_paths.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.rsc_diag_fill_staging.argtypes = [vp, C.c_int]
+    L.rsc_diag_fill_staging.restype = C.c_int64
     L.rsc_context_set_eig_split.argtypes = [vp, C.c_int]
     L.rsc_context_set_sim3opt_helpers.argtypes = [vp, C.c_int]
     L.rsc_pnp_create.argtypes = [vp, C.POINTER(PnPProblem), C.c_uint32, C.POINTER(vp)]
@@ -1227,6 +1230,14 @@ class Context:
         out = (C.c_int64 * 3)()
         _check(load_library().rsc_diag_round_paths(self.h, out), "round_paths")
         return dict(args=int(out[0]), blob=int(out[1]), table_uploads=int(out[2]))
+
+    def fill_staging(self, byte: int) -> int:
+        """Diagnostic: fill every staging buffer of the batched calls (device arenas, LM input and result
+        buffers, and their pinned mirrors) with `byte` over its whole capacity; returns the bytes filled."""
+        n = int(load_library().rsc_diag_fill_staging(self.h, int(byte)))
+        if n < 0:
+            _check(n, "fill_staging")
+        return n
 
     def set_sim3opt_helpers(self, helpers: int):
         """OptimizeSim3's form: helper workgroups per pair (the cooperative form), 0 = one workgroup

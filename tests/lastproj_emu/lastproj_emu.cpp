@@ -116,9 +116,9 @@ void lse_search_sequential(const lse_problem* p, int32_t* out, int32_t* counts) 
 }
 
 // The kernels' work (lastproj.hip): last_setup_slot for every slot, then the rounds, then the histogram over
-// all claims, the last-writer table and the nulling.  counts = nmatches, mode, rounds, claims; *fallbacks =
-// window walks taken.
-void lse_search_fixed_point(const lse_problem* p, int32_t* out, int32_t* counts, int32_t* fallbacks) {
+// all claims, the last-writer table and the nulling.  counts = nmatches, mode, rounds, claims; walks[0] =
+// window walks taken, walks[1] = the most of them in one round.
+void lse_search_fixed_point_walks(const lse_problem* p, int32_t* out, int32_t* counts, int32_t* walks) {
     Views v;
     make_views(*p, v);
     const int mode = last_mode(p->Tcw_cur, p->Tcw_last, p->mb);
@@ -141,7 +141,7 @@ void lse_search_fixed_point(const lse_problem* p, int32_t* out, int32_t* counts,
         last_setup_slot(Q, i, p->th);
         n_eligible += rec[i].cells >= 0;
     }
-    const int done = emu_rounds(LastRounds{Q, mode}, p->nf, Q.claim, n_eligible, fallbacks);
+    const int done = emu_rounds(LastRounds{Q, mode}, p->nf, Q.claim, n_eligible, walks, walks + 1);
     int hs[kProjHistoLength] = {}, keep[3] = {-1, -1, -1};
     if (p->check_ori) {
         for (int i = 0; i < p->nl; ++i) {
@@ -173,6 +173,13 @@ void lse_search_fixed_point(const lse_problem* p, int32_t* out, int32_t* counts,
     counts[1] = mode;
     counts[2] = done;
     counts[3] = total;
+}
+
+// the same; *fallbacks (may be NULL) = window walks taken
+void lse_search_fixed_point(const lse_problem* p, int32_t* out, int32_t* counts, int32_t* fallbacks) {
+    int32_t walks[2];
+    lse_search_fixed_point_walks(p, out, counts, walks);
+    if (fallbacks) *fallbacks = walks[0];
 }
 
 }  // extern "C"

@@ -47,6 +47,8 @@ def lib(o3: bool = False):
         L.lse_search_sequential.restype = None
         L.lse_search_fixed_point.argtypes = [C.POINTER(Problem), i32p, i32p, C.POINTER(C.c_int32)]
         L.lse_search_fixed_point.restype = None
+        L.lse_search_fixed_point_walks.argtypes = [C.POINTER(Problem), i32p, i32p, i32p]
+        L.lse_search_fixed_point_walks.restype = None
         L.lse_mode.argtypes = [f32p, f32p, C.c_float]
         _libs[o3] = L
     return _libs[o3]
@@ -82,13 +84,13 @@ def _run(p, fixed_point: bool, o3: bool = False, packed=None):
     q, keep = pack(p) if packed is None else packed
     out = np.full(max(p.frame.n, 1), -7, np.int32)
     counts = np.zeros(4, np.int32)
-    walks = C.c_int32()
+    walks = np.zeros(2, np.int32)  # all window walks, the most in one round
     if fixed_point:
-        lib(o3).lse_search_fixed_point(C.byref(q), out, counts, C.byref(walks))
+        lib(o3).lse_search_fixed_point_walks(C.byref(q), out, counts, walks)
     else:
         lib(o3).lse_search_sequential(C.byref(q), out, counts)
     return dict(out=out[:p.frame.n], nmatches=int(counts[0]), mode=int(counts[1]), rounds=int(counts[2]),
-                claims=int(counts[3]), walks=walks.value)
+                claims=int(counts[3]), walks=int(walks[0]), max_round_walks=int(walks[1]))
 
 
 def search_sequential(p, o3: bool = False, packed=None):

@@ -118,8 +118,9 @@ void lpe_search_sequential(const lpe_problem* p, int32_t* out, LpTrack* track, i
 }
 
 // The kernels' work (localproj.hip): lp_setup_point for every point, then the rounds.  counts = nmatches,
-// nToMatch, rounds; *fallbacks = window walks taken.
-void lpe_search_fixed_point(const lpe_problem* p, int32_t* out, LpTrack* track, int32_t* counts, int32_t* fallbacks) {
+// nToMatch, rounds; walks[0] = window walks taken, walks[1] = the most of them in one round.
+void lpe_search_fixed_point_walks(const lpe_problem* p, int32_t* out, LpTrack* track, int32_t* counts,
+                                  int32_t* walks) {
     Views v;
     make_views(*p, v);
     std::vector<int> claim((size_t)p->np + 1);
@@ -146,9 +147,16 @@ void lpe_search_fixed_point(const lpe_problem* p, int32_t* out, LpTrack* track, 
         n_to_match += rec[i].in_view;
         n_eligible += rec[i].cells >= 0;
     }
-    counts[2] = emu_rounds(LpRounds{Q, p->nn_ratio}, p->nf, Q.claim, n_eligible, fallbacks);
+    counts[2] = emu_rounds(LpRounds{Q, p->nn_ratio}, p->nf, Q.claim, n_eligible, walks, walks + 1);
     counts[0] = finish(*p, claim, out);
     counts[1] = n_to_match;
+}
+
+// the same; *fallbacks (may be NULL) = window walks taken
+void lpe_search_fixed_point(const lpe_problem* p, int32_t* out, LpTrack* track, int32_t* counts, int32_t* fallbacks) {
+    int32_t walks[2];
+    lpe_search_fixed_point_walks(p, out, track, counts, walks);
+    if (fallbacks) *fallbacks = walks[0];
 }
 
 // the streaming update of ORBmatcher.cpp:73-85 over a sequence: res = bestDist, bestLevel, bestDist2,

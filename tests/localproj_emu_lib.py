@@ -42,6 +42,8 @@ def lib(o3: bool = False):
         L.lpe_search_sequential.restype = None
         L.lpe_search_fixed_point.argtypes = [C.POINTER(Problem), i32p, C.c_void_p, i32p, C.POINTER(C.c_int32)]
         L.lpe_search_fixed_point.restype = None
+        L.lpe_search_fixed_point_walks.argtypes = [C.POINTER(Problem), i32p, C.c_void_p, i32p, i32p]
+        L.lpe_search_fixed_point_walks.restype = None
         L.lpe_top2.argtypes = [C.c_int, i32p, i32p, i32p]
         L.lpe_top2.restype = None
         L.lpe_accepts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]
@@ -93,13 +95,13 @@ def _run(p, track, fixed_point: bool, o3: bool = False):
     out = np.full(max(p.frame.n, 1), -7, np.int32)
     tr = np.zeros(max(p.pts.n, 1), lr.TRACK)
     counts = np.zeros(3, np.int32)
-    walks = C.c_int32()
+    walks = np.zeros(2, np.int32)  # all window walks, the most in one round
     if fixed_point:
-        lib(o3).lpe_search_fixed_point(C.byref(q), out, tr.ctypes.data, counts, C.byref(walks))
+        lib(o3).lpe_search_fixed_point_walks(C.byref(q), out, tr.ctypes.data, counts, walks)
     else:
         lib(o3).lpe_search_sequential(C.byref(q), out, tr.ctypes.data, counts)
     return dict(out=out[:p.frame.n], track=tr[:p.pts.n], nmatches=int(counts[0]), n_to_match=int(counts[1]),
-                rounds=int(counts[2]), walks=walks.value)
+                rounds=int(counts[2]), walks=int(walks[0]), max_round_walks=int(walks[1]))
 
 
 def search_sequential(p, track=None, o3: bool = False):

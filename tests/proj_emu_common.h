@@ -35,17 +35,20 @@ void make_frame_view(const P& p, int n, const float* angle, EmuFrame& v) {
 // The rounds of proj_rounds for matcher m: every round rebuilds the owner table from the blocking claims of the
 // round before (a sequential atomicMin) and recomputes every point against it, from its cache or by walking
 // its window; stops when no claim changed.  claim: -1 on entry, the fixed point on return.  Returns the rounds
-// run; *walks (may be NULL) counts the window walks.
+// run; *walks (may be NULL) counts the window walks and *max_round_walks (may be NULL) the most of them in one
+// round: the length the kernel's walk list (kProjWalkCap, rsc_projrounds.h) would need.
 template <class M>
-int emu_rounds(const M& m, int n_features, int32_t* claim, int n_eligible, int32_t* walks) {
+int emu_rounds(const M& m, int n_features, int32_t* claim, int n_eligible, int32_t* walks,
+               int32_t* max_round_walks = nullptr) {
     const int n = m.n_points();
     std::vector<int> owner((size_t)n_features + 1), next((size_t)n + 1);
-    int done = 0, walked = 0;
+    int done = 0, walked = 0, most = 0;
     for (int r = 0; r < n_eligible + 1; ++r) {
         for (int f = 0; f < n_features; ++f) owner[f] = m.entry_occupied(f) ? kProjOccupied : kProjFree;
         for (int i = 0; i < n; ++i)
             if (claim[i] >= 0 && m.blocks(i) && i < owner[claim[i]]) owner[claim[i]] = i;
         bool changed = false;
+        const int before = walked;
         for (int i = 0; i < n; ++i) {
             int b = m.pick(i, owner.data());
             if (b == kProjSkip) b = -1;
@@ -57,10 +60,12 @@ int emu_rounds(const M& m, int n_features, int32_t* claim, int n_eligible, int32
             changed |= b != claim[i];
         }
         std::memcpy(claim, next.data(), sizeof(int32_t) * (size_t)n);
+        if (walked - before > most) most = walked - before;
         ++done;
         if (!changed) break;
     }
     if (walks) *walks = walked;
+    if (max_round_walks) *max_round_walks = most;
     return done;
 }
 
