@@ -12,7 +12,7 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
      facade_lastproj_test facade_triang_test arena_test viewimage_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test ref_dbow2 \
-     mpupdate_emu facade_mpupdate_test stereo_emu facade_stereo_test
+     mpupdate_emu facade_mpupdate_test stereo_emu facade_stereo_test localba_emu localba_test facade_localba_test
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -48,6 +48,13 @@ $(LIBDIR)/stereo.o: $(CSRC)/stereo.hip $(HDRS)
 		2> $(LIBDIR)/stereo.resources.txt || { cat $(LIBDIR)/stereo.resources.txt >&2; exit 1; }
 	@grep -v 'Rpass-analysis=kernel-resource-usage' $(LIBDIR)/stereo.resources.txt >&2 || true
 
+# localba.hip likewise (the stage kernels of LocalBundleAdjustment: DESIGN.md §2.17)
+$(LIBDIR)/localba.o: $(CSRC)/localba.hip $(HDRS)
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -fno-caret-diagnostics -c $< -o $@ \
+		2> $(LIBDIR)/localba.resources.txt || { cat $(LIBDIR)/localba.resources.txt >&2; exit 1; }
+	@grep -v 'Rpass-analysis=kernel-resource-usage' $(LIBDIR)/localba.resources.txt >&2 || true
+
 $(LIBDIR)/librsc.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
@@ -61,12 +68,15 @@ $(LIBDIR)/librsc_spin1.so: $(OBJS:%/kernels.o=%/kernels_spin1.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^
 
 FACADE_TESTS = facade_test facade_proj_test facade_loopproj_test facade_localproj_test facade_lastproj_test \
-               facade_triang_test facade_fusekf_test facade_voc_test facade_mpupdate_test facade_stereo_test
+               facade_triang_test facade_fusekf_test facade_voc_test facade_mpupdate_test facade_stereo_test facade_localba_test
 
 $(FACADE_TESTS): %: $(LIBDIR)/%
 
 $(FACADE_TESTS:%=$(LIBDIR)/%): $(LIBDIR)/%: tests/cpp/%.cpp $(CSRC)/facade/*.hpp $(LIBDIR)/librsc.so
 	g++ -O2 -std=c++17 -Iinclude -I$(CSRC)/facade -o $@ $< -L$(LIBDIR) -lrsc -Wl,-rpath,'$$ORIGIN'
+
+# the LocalBundleAdjustment facade test also compiles the host restatement it compares against
+$(LIBDIR)/facade_localba_test: tests/localba_emu/localba_emu.cpp $(CSRC)/rsc_localba.h
 
 # TEST-ONLY host programs: tridiag_qr with and without the mirror() / any_lane() hooks of its
 # rotation sink (tests/test_cpu_chase_mirror.py); the second build runs under the host sanitizers
@@ -137,6 +147,21 @@ $(LIBDIR)/seed_window_test_san: $(SEED_WINDOW_DEPS)
 	mkdir -p $(LIBDIR)
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
 
+# TEST-ONLY host program: the sequential LocalBundleAdjustment restatement (tests/localba_emu) on four scenes of
+# its own (tests/test_cpu_localba.py); the second build runs under the host sanitizers
+localba_test: $(LIBDIR)/localba_test $(LIBDIR)/localba_test_san
+
+LOCALBA_DEPS = tests/cpp/localba_test.cpp tests/localba_emu/localba_emu.cpp $(CSRC)/rsc_localba.h $(CSRC)/rsc_poseopt.h \
+               $(CSRC)/rsc_core.h $(CSRC)/rsc_math.h include/rsc.h
+
+$(LIBDIR)/localba_test: $(LOCALBA_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/localba_test_san: $(LOCALBA_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -174,10 +199,14 @@ mpupdate_emu:
 stereo_emu:
 	$(MAKE) -s -C tests/stereo_emu
 
+localba_emu:
+	$(MAKE) -s -C tests/localba_emu
+
 clean:
 	rm -rf $(LIBDIR) oracle/build oracle/_ref tests/hostemu/build tests/frameproj_emu/build tests/kfproj_emu/build tests/bowvoc_emu/build \
 	       tests/localproj_emu/build tests/lastproj_emu/build tests/triang_emu/build tests/fusekf_emu/build tests/mpupdate_emu/build \
-	       tests/stereo_emu/build
+	       tests/stereo_emu/build tests/localba_emu/build
 
+.PHONY: localba_emu localba_test facade_localba_test
 .PHONY: all oracle ref_dbow2 hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu mpupdate_emu stereo_emu facade_stereo_test facade_mpupdate_test facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
         facade_voc_test chase_mirror_test arena_test viewimage_test rounds_test seed_window_test clean

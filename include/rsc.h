@@ -447,6 +447,92 @@ typedef struct {
 int rsc_optimize_sim3_many(rsc_context* ctx, const rsc_sim3opt_problem* problems, int count,
                            rsc_sim3opt_result* out, uint8_t* const* keep);
 
+/* ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cpp:426-787) ----------------------------------
+ * The local mapping thread's bundle adjustment, called after SearchInNeighbors (LocalMapping.cpp): g2o
+ * Levenberg-Marquardt over the local KeyFrames (VertexSE3Expmap; the fixed cameras and KeyFrame 0 fixed) and the
+ * local MapPoints (VertexSBAPointXYZ, marginalised) with EdgeSE3ProjectXYZ (u_right < 0) and
+ * EdgeStereoSE3ProjectXYZ edges, BlockSolver_6_3's Schur complement, Huber kernels (delta sqrt(5.991) /
+ * sqrt(7.815) as float): optimize(5), classification (chi2 > 5.991 / 7.815 or depth <= 0 -> level 1, kernels
+ * removed), initializeOptimization(0), optimize(10), final classification into vToErase, recovery.
+ * The caller builds lLocalKeyFrames / lFixedCameras / lLocalMapPoints (:430-483) and passes plain arrays.
+ * The reduced pose system is solved by an LDL^T without pivoting in Hessian-index order over the dense
+ * matrix (DESIGN.md §2.17 states the arithmetic); the reference's LinearSolverEigen orders it by AMD first, so
+ * the two differ at rounding level, and parity with a g2o / Eigen build is unpinned. */
+#define RSC_LOCALBA_MAX_FREE_KFS 64   /* a 384 x 384 reduced system */
+#define RSC_LOCALBA_MAX_KFS 4160      /* free and fixed together */
+#define RSC_LOCALBA_MAX_POINTS 16384
+#define RSC_LOCALBA_MAX_EDGES 131072
+typedef struct {
+    int32_t n_kfs;             /* lLocalKeyFrames and lFixedCameras, in any order */
+    const int64_t* kf_id;      /* [n_kfs] mnId, unique; the Hessian index of a free KeyFrame is its rank by kf_id */
+    const uint8_t* fixed;      /* [n_kfs] mnId == 0 or one of lFixedCameras */
+    const float* Tcw;          /* [n_kfs][16] row-major GetPose() */
+    const float* cam;          /* [n_kfs][5] fx, fy, cx, cy, mbf */
+    int32_t n_points;          /* lLocalMapPoints, in list order */
+    const int64_t* mp_id;      /* [n_points] mnId, unique; the landmark index is the rank by mp_id */
+    const float* pos;          /* [n_points][3] GetWorldPos() */
+    const uint8_t* bad;        /* [n_points] isBad() as the classification loops read it (:670,688,717,733) */
+    const int32_t* obs_begin;  /* [n_points + 1] CSR over the points, obs_begin[0] == 0: the edges in the caller's
+                                  iteration order of GetObservations(), bad KeyFrames left out (:574) */
+    const int32_t* obs_kf;     /* [n_edges] index into the KeyFrames; a point names a KeyFrame at most once */
+    const float* uv;           /* [n_edges][2] mvKeysUn[idx].pt */
+    const float* u_right;      /* [n_edges] mvuRight[idx]; < 0: a monocular edge */
+    const float* inv_sigma2;   /* [n_edges] mvInvLevelSigma2[octave] */
+} rsc_localba_problem;
+
+typedef struct {               /* any member may be NULL */
+    float* Tcw;                /* [n_kfs][16] Converter::toIso(estimate) as float; fixed KeyFrames: the input bytes */
+    float* pos;                /* [n_points][3] estimate.cast<float>() */
+    uint8_t* edge_flags;       /* [n_edges] bit 0: level 1 after the first optimize(); bit 1: in vToErase */
+    int32_t* erase;            /* [n_edges] the first n_erase entries: vToErase as edge indices, mono edges first,
+                                  then stereo, each in edge order */
+} rsc_localba_out;
+
+typedef struct {
+    int32_t n_vertices, n_points, n_edges; /* active vertices (fixed KeyFrames included), points among them, edges */
+    int32_t lm_iterations, lm_trials;
+    double chi2_first, chi2_last;          /* activeRobustChi2 at the first solve() and of the estimates left */
+} rsc_localba_phase;
+
+#define RSC_LOCALBA_NO_EDGE_1 1  /* status bits: the first optimize() had no active edge (no edge at all) */
+#define RSC_LOCALBA_NO_EDGE_2 2  /* every edge was level 1: initializeOptimization(0) fails, optimize(10) returns */
+#define RSC_LOCALBA_NO_FREE_KF 4 /* no free KeyFrame among the active vertices of the first optimize() */
+typedef struct {
+    int32_t n_erase, n_level1, status;
+    rsc_localba_phase phase[2];
+    int32_t branches[12];      /* LM branch counters over both phases: iterations, trials, zero pivot, tempChi
+                                  non-finite, rho NaN, rejected, qmax == 10, rho == 0, nBad >= 3, phase without
+                                  an active edge, vertices dropped from the active set, level-1 edges not erased */
+} rsc_localba_result;
+
+/* LocalBundleAdjustment on `count` problems, one after another; out (may be NULL) and result (may be NULL) are
+ * arrays of `count`.  Each stage of a Levenberg trial is a launch spread over the device; the host reads one
+ * small record per trial.  With timing on, rsc_context_last_kernel_timing's [2] is the device time of the call.
+ *
+ * Quirks reproduced: a level-1 edge's chi2() is never recomputed in the second optimize(), so the final loop reads
+ * its first-phase value while isDepthPositive() reads the final estimates (an edge set aside for depth alone can
+ * leave vToErase); the edges of a `bad` point are skipped by both classification loops and keep level 0 and
+ * their kernel; a vertex without a level-0 edge leaves the active set and the indices are rebuilt; the edges'
+ * _error after optimize() is that of the last trial, accepted or not.  The stop flag is not an input: the caller
+ * reads *pbStopFlag before the call.
+ *
+ * Limits (checked before any launch; outputs untouched, the context stays usable): RSC_ERR_ARG for a NULL array,
+ * a kf_id or mp_id that is not unique, obs_begin not ascending from 0, obs_kf out of range, or a point naming a
+ * KeyFrame twice; RSC_ERR_UNSUPPORTED above RSC_LOCALBA_MAX_FREE_KFS free KeyFrames, RSC_LOCALBA_MAX_KFS
+ * KeyFrames, RSC_LOCALBA_MAX_POINTS points or RSC_LOCALBA_MAX_EDGES edges.  count == 0 is RSC_OK.
+ *
+ * Degenerate problems.  No edge: initializeOptimization() fails and both optimize() calls return at once; free
+ * KeyFrames come back as the quaternion round trip of their entry pose, points as given.  No free KeyFrame
+ * with edges: the points alone are optimised (an empty reduced system solves trivially).  Every edge level 1
+ * after the first phase: the second optimize() returns at once and the final loop reads the first phase's
+ * chi2.  A vertex that was never active is recovered all the same (pose: quaternion round trip).  The update
+ * vector starts at zero in each optimize() (the reference allocates it without clearing it; it matters only when
+ * the first reduced solve of a phase meets a zero pivot).  NaN / Inf / z == 0 inputs are taken as given: a
+ * non-finite chi2 makes rho NaN, no trial is accepted and every iteration runs one trial.  No input makes the
+ * call loop: every loop is bounded by the counts and the (5 + 10) iterations x 10 trials schedule. */
+int rsc_local_bundle_adjustment_many(rsc_context* ctx, const rsc_localba_problem* problems, int count,
+                                     const rsc_localba_out* out, rsc_localba_result* result);
+
 /* ---- ORBmatcher::SearchByBoW (src/ORBmatcher.cpp:110-240, :354-488) -----------------------------
  * The producer of every RANSAC correspondence set: Hamming-256 matching of ORB descriptors that
  * share a DBoW2 FeatureVector node, with the nearest-neighbour ratio test and the rotation-histogram
@@ -1173,6 +1259,12 @@ int rsc_diag_bow_phase_stamps(rsc_context* ctx, uint64_t* out, int cap);
  * result buffers, each with its pinned mirror.  Resident views, KeyFrame databases and solvers are not
  * touched.  Returns the number of bytes filled (device and pinned together), or a negative RSC_ERR_*. */
 int64_t rsc_diag_fill_staging(rsc_context* ctx, int byte);
+
+/* Device milliseconds per stage, summed over the launches of the last rsc_local_bundle_adjustment_many that ran
+ * with timing on (HIP events around every launch): out[0..10] = linearise and build, vertex sums, iteration head,
+ * point inverses, Schur complement, reduced solve, trial errors, back-substitution and update, trial tail, restore,
+ * classification.  cap >= 11. */
+int rsc_diag_localba_stages(rsc_context* ctx, double* out, int cap);
 
 /* ---- glibc rand() helpers (Thirdparty/DBoW2/DUtils/Random.cpp:33-50) -------------------------- */
 /* First n rand() outputs after srand(seed), produced with the device jump table (parity hook). */

@@ -10,9 +10,17 @@
 //     int nGood = rsc_orb::PoseOptimization(&mCurrentFrame);       // Tracking.cpp:621,745,787,1284
 // Slots with mvuRight >= 0 become EdgeStereoSE3ProjectXYZOnlyPose edges (Optimizer.cpp:290-323), the
 // others monocular edges, exactly as the reference's stereo_euroc / stereo_kitti builds run it.
+//
+// Optimizer::LocalBundleAdjustment (:426-787) is at the end of this file: the lists are built here, the two-phase
+// Levenberg-Marquardt runs in rsc_local_bundle_adjustment_many, and the erase replay and the write-back happen
+// here under the map mutex.
 #pragma once
+#include <map>
+#include <mutex>
+#include <type_traits>
 #include <vector>
 #include "rsc_context.hpp"
+#include "MapPoint.hpp"
 
 namespace rsc_orb {
 
@@ -198,6 +206,133 @@ int OptimizeSim3(KFPtr pKF1, KFPtr pKF2, std::vector<MPPtr>& vpMatches1, Sim3T& 
     uint8_t* k = in.keep.data();
     check(rsc_optimize_sim3_many(thread_context(), &in.pb, 1, &r, &k), "OptimizeSim3");
     return in.apply(vpMatches1, g2oS12, r);
+}
+
+// ---- Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (Optimizer.cpp:426-787; LocalMapping.cpp) --------
+// KeyFrame needs mnId, mnBALocalForKF, mnBAFixedForKF, isBad(), GetVectorCovisibleKeyFrames(), GetMapPointMatches(),
+// GetPose() (indexable with (r, c), writable: Eigen::Isometry3f or cv-like) and SetPose(of that type), fx, fy, cx, cy,
+// mbf, mvKeysUn[i].pt / .octave, mvuRight, mvInvLevelSigma2, EraseMapPointMatch(pMP), and what UpdateMapPoints reads
+// (facade/MapPoint.hpp).  MapPoint needs mnId, mnBALocalForKF, isBad(), GetObservations() (the std::map, iterated in
+// map order as the reference does), GetWorldPos() (indexable with (i), writable) and SetWorldPos(of that type),
+// EraseObservation(pKF), and UpdateMapPoints' two setters.  Map needs mMutexMapUpdate.
+//
+// What differs from the reference: *pbStopFlag is read once, where the reference first reads it
+// (:642-647), and both optimize() calls run otherwise; isBad() of a point is read once, when the problem is built,
+// for both classification loops; KeyFrame 0 keeps its pose bytes (the reference writes the quaternion round trip
+// of its fixed estimate); the per-point UpdateNormalAndDepth() of :783 is one UpdateMapPoints(points, 2) call.
+// A problem over the limits of rsc_local_bundle_adjustment_many (include/rsc.h) throws through check().
+template <class KFPtr, class MapPtr>
+void LocalBundleAdjustment(KFPtr pKF, bool* pbStopFlag, MapPtr pMap) {
+    using MPPtr = typename std::decay<decltype(pKF->GetMapPointMatches()[0])>::type;
+    // Local KeyFrames: first breadth search from the current KeyFrame (:430-443)
+    std::vector<KFPtr> lLocalKeyFrames;
+    lLocalKeyFrames.push_back(pKF);
+    pKF->mnBALocalForKF = pKF->mnId;
+    const auto vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+    for (const auto& pKFi : vNeighKFs) {
+        pKFi->mnBALocalForKF = pKF->mnId;
+        if (!pKFi->isBad()) lLocalKeyFrames.push_back(pKFi);
+    }
+    // Local MapPoints seen in local KeyFrames (:448-463)
+    std::vector<MPPtr> lLocalMapPoints;
+    for (const auto& k : lLocalKeyFrames) {
+        const auto vpMPs = k->GetMapPointMatches();
+        for (const auto& pMP : vpMPs)
+            if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
+                lLocalMapPoints.push_back(pMP);
+                pMP->mnBALocalForKF = pKF->mnId;
+            }
+    }
+    // Fixed KeyFrames: they see local MapPoints but are not local (:468-483)
+    std::vector<KFPtr> lFixedCameras;
+    for (const auto& pMP : lLocalMapPoints) {
+        const auto observations = pMP->GetObservations();
+        for (const auto& o : observations) {
+            const auto& pKFi = o.first;
+            if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                pKFi->mnBAFixedForKF = pKF->mnId;
+                if (!pKFi->isBad()) lFixedCameras.push_back(pKFi);
+            }
+        }
+    }
+    // vertices (:505-529) and edges (:557-638) as arrays
+    std::vector<KFPtr> kfs(lLocalKeyFrames);
+    kfs.insert(kfs.end(), lFixedCameras.begin(), lFixedCameras.end());
+    const int K = (int)kfs.size(), nLocal = (int)lLocalKeyFrames.size(), N = (int)lLocalMapPoints.size();
+    std::vector<int64_t> kf_id((size_t)K), mp_id((size_t)N);
+    std::vector<uint8_t> fixed((size_t)K), bad((size_t)(N > 0 ? N : 1));
+    std::vector<float> Tcw(16 * (size_t)K), cam(5 * (size_t)K), pos(3 * (size_t)(N > 0 ? N : 1));
+    std::map<const void*, int> index;
+    for (int k = 0; k < K; ++k) {
+        const auto& kf = kfs[k];
+        kf_id[k] = (int64_t)kf->mnId;
+        fixed[k] = (k >= nLocal || kf->mnId == 0) ? 1 : 0;
+        const auto T = kf->GetPose();
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) Tcw[16 * (size_t)k + 4 * r + c] = T(r, c);
+        const float cm[5] = {kf->fx, kf->fy, kf->cx, kf->cy, kf->mbf};
+        for (int j = 0; j < 5; ++j) cam[5 * (size_t)k + j] = cm[j];
+        index[(const void*)&*kf] = k;
+    }
+    std::vector<int32_t> obs_begin(1, 0), obs_kf;
+    std::vector<float> uv, ur, inv;
+    for (int p = 0; p < N; ++p) {
+        const auto& pMP = lLocalMapPoints[p];
+        mp_id[p] = (int64_t)pMP->mnId;
+        bad[p] = pMP->isBad() ? 1 : 0;
+        const auto X = pMP->GetWorldPos();
+        for (int j = 0; j < 3; ++j) pos[3 * (size_t)p + j] = X(j);
+        const auto observations = pMP->GetObservations();
+        for (const auto& o : observations) {
+            const auto& pKFi = o.first;
+            if (pKFi->isBad()) continue;  // :574
+            const auto it = index.find((const void*)&*pKFi);
+            if (it == index.end()) continue;  // not reachable: every observer that is not bad is local or fixed
+            const auto& kp = pKFi->mvKeysUn[o.second];
+            obs_kf.push_back(it->second);
+            uv.push_back(kp.pt.x);
+            uv.push_back(kp.pt.y);
+            ur.push_back(pKFi->mvuRight[o.second]);
+            inv.push_back(pKFi->mvInvLevelSigma2[kp.octave]);
+        }
+        obs_begin.push_back((int32_t)obs_kf.size());
+    }
+    if (pbStopFlag && *pbStopFlag) return;  // :642-647
+    const size_t E = obs_kf.size();
+    const float zero = 0.0f;
+    const int32_t izero = 0;
+    rsc_localba_problem q;
+    q.n_kfs = K; q.kf_id = kf_id.data(); q.fixed = fixed.data(); q.Tcw = Tcw.data(); q.cam = cam.data();
+    q.n_points = N; q.mp_id = mp_id.data(); q.pos = pos.data(); q.bad = bad.data(); q.obs_begin = obs_begin.data();
+    q.obs_kf = E ? obs_kf.data() : &izero; q.uv = E ? uv.data() : &zero; q.u_right = E ? ur.data() : &zero;
+    q.inv_sigma2 = E ? inv.data() : &zero;
+    std::vector<float> TcwOut(16 * (size_t)K), posOut(3 * (size_t)(N > 0 ? N : 1));
+    std::vector<int32_t> erase(E > 0 ? E : 1);
+    std::vector<int32_t> edge_point(E > 0 ? E : 1);
+    for (int p = 0; p < N; ++p)
+        for (int e = obs_begin[p]; e < obs_begin[p + 1]; ++e) edge_point[e] = p;
+    const rsc_localba_out o{TcwOut.data(), posOut.data(), nullptr, erase.data()};
+    rsc_localba_result res;
+    check(rsc_local_bundle_adjustment_many(thread_context(), &q, 1, &o, &res), "LocalBundleAdjustment");
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);  // :745
+    for (int i = 0; i < res.n_erase; ++i) {  // :747-762, vToErase: the mono edges, then the stereo ones
+        const auto& pKFi = kfs[obs_kf[erase[i]]];
+        const auto& pMPi = lLocalMapPoints[edge_point[erase[i]]];
+        pKFi->EraseMapPointMatch(pMPi);
+        pMPi->EraseObservation(pKFi);
+    }
+    for (int k = 0; k < nLocal; ++k) {  // :768-774
+        auto T = kfs[k]->GetPose();
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) T(r, c) = TcwOut[16 * (size_t)k + 4 * r + c];
+        kfs[k]->SetPose(T);
+    }
+    for (int p = 0; p < N; ++p) {  // :778-784
+        auto X = lLocalMapPoints[p]->GetWorldPos();
+        for (int j = 0; j < 3; ++j) X(j) = posOut[3 * (size_t)p + j];
+        lLocalMapPoints[p]->SetWorldPos(X);
+    }
+    UpdateMapPoints(lLocalMapPoints, 2);  // pMP->UpdateNormalAndDepth() of :783, in one call
 }
 
 }  // namespace rsc_orb

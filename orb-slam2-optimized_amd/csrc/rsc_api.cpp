@@ -1169,6 +1169,7 @@ int64_t rsc_diag_fill_staging(rsc_context* C, int byte) {
     RSC_HIP(fill(C->d_po_res, C->h_po_res));
     RSC_HIP(fill(C->d_so_in, C->h_so_in));
     RSC_HIP(fill(C->d_so_res, C->h_so_res));
+    RSC_HIP(fill(C->d_lba, C->h_lba));
     RSC_HIP(hipStreamSynchronize(C->stream));
     return total;
 }

@@ -137,6 +137,12 @@ struct rsc_context {
     DevBuf<char> d_po_res;
     PinBuf<char> h_po_in;
     PinBuf<char> h_po_res;
+    // LocalBundleAdjustment: problem | plan | estimates and work | results (device, pinned mirror)
+    DevBuf<char> d_lba;
+    PinBuf<char> h_lba;
+    // device milliseconds per stage of the last rsc_local_bundle_adjustment_many with timing on
+    // (rsc_diag_localba_stages)
+    double lba_stage_ms[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // SearchBySim3: packed KeyFrames + pair table + scratch + outputs (device, pinned mirror)
     DevBuf<char> d_s3m;
     PinBuf<char> h_s3m;

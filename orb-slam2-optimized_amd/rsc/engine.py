@@ -68,6 +68,7 @@ EXPORTED = [
     "rsc_update_map_points_many", "rsc_mpview_download",
     "rsc_compute_stereo_matches_many",
     "rsc_diag_fill_staging",
+    "rsc_local_bundle_adjustment_many", "rsc_diag_localba_stages",
 ]
 
 # include/rsc.h RSC_GATE_*
@@ -720,6 +721,114 @@ def update_map_points_many(ctx: Context, kfs, updates, what: int = 3, dst=None, 
     return res if out is not None else {k: a[:n] for k, a in res.items()}
 
 
+class LocalBAProblem(C.Structure):
+    """rsc_localba_problem (include/rsc.h)."""
+    _fields_ = [("n_kfs", C.c_int32), ("kf_id", C.c_void_p), ("fixed", C.c_void_p), ("Tcw", C.c_void_p),
+                ("cam", C.c_void_p), ("n_points", C.c_int32), ("mp_id", C.c_void_p), ("pos", C.c_void_p),
+                ("bad", C.c_void_p), ("obs_begin", C.c_void_p), ("obs_kf", C.c_void_p), ("uv", C.c_void_p),
+                ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p)]
+
+
+class LocalBAOut(C.Structure):
+    """rsc_localba_out (include/rsc.h)."""
+    _fields_ = [("Tcw", C.c_void_p), ("pos", C.c_void_p), ("edge_flags", C.c_void_p), ("erase", C.c_void_p)]
+
+
+class LocalBAPhase(C.Structure):
+    """rsc_localba_phase (include/rsc.h)."""
+    _fields_ = [("n_vertices", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
+                ("lm_iterations", C.c_int32), ("lm_trials", C.c_int32), ("chi2_first", C.c_double),
+                ("chi2_last", C.c_double)]
+
+
+class LocalBAResult(C.Structure):
+    """rsc_localba_result (include/rsc.h)."""
+    _fields_ = [("n_erase", C.c_int32), ("n_level1", C.c_int32), ("status", C.c_int32), ("phase", LocalBAPhase * 2),
+                ("branches", C.c_int32 * 12)]
+
+
+LOCALBA_MAX_FREE_KFS, LOCALBA_MAX_KFS, LOCALBA_MAX_POINTS, LOCALBA_MAX_EDGES = 64, 4160, 16384, 131072
+LOCALBA_BRANCHES = ("iterations", "trials", "zero_pivot", "chi_non_finite", "rho_nan", "rejected", "qmax", "rho_zero",
+                    "nbad", "no_active_edge", "vertex_dropped", "stale_kept")
+# what local_bundle_adjustment puts into its outputs before the call (a refused call leaves them)
+LOCALBA_FILL = dict(Tcw=np.float32(-77.0), pos=np.float32(-77.0), edge_flags=0xA5, erase=-7)
+
+
+def localba_pack(problem):
+    """The ctypes image of a LocalBundleAdjustment problem: a dict (rsc/synth.make_localba_scene's keys kf_id int64
+    [K], fixed uint8 [K], Tcw float32 [K,16], cam float32 [K,5], mp_id int64 [N], pos float32 [N,3], bad uint8 [N],
+    obs_begin int32 [N+1], obs_kf int32 [E], uv float32 [E,2], u_right float32 [E], inv_sigma2 float32 [E]).
+    Returns (LocalBAProblem, the arrays it points at)."""
+    dt = dict(kf_id=np.int64, fixed=np.uint8, Tcw=np.float32, cam=np.float32, mp_id=np.int64, pos=np.float32,
+              bad=np.uint8, obs_begin=np.int32, obs_kf=np.int32, uv=np.float32, u_right=np.float32, inv_sigma2=np.float32)
+    keep = {}
+    for k, t in dt.items():
+        a = np.ascontiguousarray(problem[k], t).reshape(-1)
+        keep[k] = a if a.size else np.zeros(1, t)
+    q = LocalBAProblem()
+    q.n_kfs = int(np.size(problem["kf_id"]))
+    q.n_points = int(np.size(problem["mp_id"]))
+    for k, a in keep.items():
+        setattr(q, k, a.ctypes.data)
+    return q, keep
+
+
+def localba_outputs(problem):
+    """Output arrays of one problem, holding LOCALBA_FILL."""
+    K, N = int(np.size(problem["kf_id"])), int(np.size(problem["mp_id"]))
+    E = int(np.size(problem["obs_kf"]))
+    F = LOCALBA_FILL
+    return dict(Tcw=np.full((max(K, 1), 16), F["Tcw"], np.float32), pos=np.full((max(N, 1), 3), F["pos"], np.float32),
+                edge_flags=np.full(max(E, 1), F["edge_flags"], np.uint8), erase=np.full(max(E, 1), F["erase"], np.int32))
+
+
+def localba_result_dict(problem, arrays, r):
+    """What a LocalBundleAdjustment call returned, as a dict (arrays cut to the problem's sizes)."""
+    K, N = int(np.size(problem["kf_id"])), int(np.size(problem["mp_id"]))
+    E = int(np.size(problem["obs_kf"]))
+    ph = [dict(n_vertices=p.n_vertices, n_points=p.n_points, n_edges=p.n_edges, lm_iterations=p.lm_iterations,
+               lm_trials=p.lm_trials, chi2_first=np.float64(p.chi2_first), chi2_last=np.float64(p.chi2_last))
+          for p in r.phase]
+    return dict(Tcw=arrays["Tcw"][:K], pos=arrays["pos"][:N], edge_flags=arrays["edge_flags"][:E],
+                erase=arrays["erase"][:r.n_erase].copy(), n_erase=r.n_erase, n_level1=r.n_level1, status=r.status,
+                phase=ph, branches=dict(zip(LOCALBA_BRANCHES, list(r.branches))))
+
+
+def local_bundle_adjustment_many(ctx: Context, problems):
+    """Optimizer::LocalBundleAdjustment (Optimizer.cpp:426-787; rsc_local_bundle_adjustment_many) on each problem
+    dict (localba_pack's keys).  Returns one dict per problem: Tcw float32 [K,16], pos float32 [N,3], edge_flags
+    uint8 [E] (bit 0 level 1 after the first optimize(), bit 1 in vToErase), erase int32 [n_erase], n_erase,
+    n_level1, status, phase (two dicts), branches."""
+    c = len(problems)
+    packed = [localba_pack(p) for p in problems]
+    arrays = [localba_outputs(p) for p in problems]
+    P = (LocalBAProblem * max(c, 1))(*[q for q, _ in packed])
+    O = (LocalBAOut * max(c, 1))()
+    for i, a in enumerate(arrays):
+        for k, v in a.items():
+            setattr(O[i], k, v.ctypes.data)
+    R = (LocalBAResult * max(c, 1))()
+    _check(load_library().rsc_local_bundle_adjustment_many(ctx.h, P, c, O, R), "rsc_local_bundle_adjustment_many")
+    return [localba_result_dict(p, a, r) for p, a, r in zip(problems, arrays, R)]
+
+
+LOCALBA_STAGES = ("build", "vertex_sums", "iteration_head", "point_inverses", "schur", "reduced_solve", "trial_errors",
+                  "update", "trial_tail", "restore", "classify")
+
+
+def localba_stage_ms(ctx: Context):
+    """Device milliseconds per stage of the last local_bundle_adjustment* call that ran with timing on
+    (rsc_diag_localba_stages), as a dict over LOCALBA_STAGES."""
+    out = (C.c_double * 11)()
+    _check(load_library().rsc_diag_localba_stages(ctx.h, out, 11), "rsc_diag_localba_stages")
+    return dict(zip(LOCALBA_STAGES, [float(v) for v in out]))
+
+
+def local_bundle_adjustment(ctx: Context, problem):
+    """local_bundle_adjustment_many on one problem."""
+    return local_bundle_adjustment_many(ctx, [problem])[0]
+
+
 class RightFeatures(C.Structure):
     """rsc_right_features (include/rsc.h)."""
     _fields_ = [("n", C.c_int32), ("kp", C.c_void_p), ("octave", C.c_void_p), ("desc", C.c_void_p)]
@@ -1008,6 +1117,9 @@ def load_library(path: str = LIB_PATH):
     L.rsc_diag_round_paths.argtypes = [vp, C.POINTER(C.c_int64)]
     L.rsc_diag_fill_staging.argtypes = [vp, C.c_int]
     L.rsc_diag_fill_staging.restype = C.c_int64
+    L.rsc_diag_localba_stages.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+    L.rsc_local_bundle_adjustment_many.argtypes = [vp, C.POINTER(LocalBAProblem), C.c_int, C.POINTER(LocalBAOut),
+                                                   C.POINTER(LocalBAResult)]
     L.rsc_context_set_eig_split.argtypes = [vp, C.c_int]
     L.rsc_context_set_sim3opt_helpers.argtypes = [vp, C.c_int]
     L.rsc_pnp_create.argtypes = [vp, C.POINTER(PnPProblem), C.c_uint32, C.POINTER(vp)]

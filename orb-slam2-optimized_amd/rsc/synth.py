@@ -1240,3 +1240,87 @@ def sample_descriptors(rng: np.random.Generator, voc: Vocabulary, n: int, mean_f
     rnd = rng.random(n) < random_frac
     out[rnd] = rng.integers(0, 256, size=(int(rnd.sum()), 32), dtype=np.uint8)
     return np.ascontiguousarray(out)
+
+
+def make_localba_scene(rng: np.random.Generator, n_free: int, n_fixed: int, n_points: int, obs_per_point=(2, 5),
+                       stereo_frac: float = 0.7, noise_px: float = 0.0, pose_perturb: float = 0.0,
+                       point_perturb: float = 0.0, outlier_frac: float = 0.0, outlier_px: float = 40.0,
+                       id_order: str = "ascending", bf: float = 40.0, near: bool = False):
+    """A LocalBundleAdjustment problem (Optimizer.cpp:426-787; engine.localba_pack's keys): n_free + n_fixed
+    KeyFrames on a sideways trajectory looking down +z, points in the frustum they share, each observed by a random
+    subset of obs_per_point = (lo, hi) KeyFrames (all of them when fewer exist).  stereo_frac of the observations
+    carry u_right, noise_px is the Gaussian pixel noise, pose_perturb / point_perturb the size of the perturbation
+    of the free poses (rad and m) and of the points (m), outlier_frac of the observations are displaced by
+    outlier_px pixels.  near: a point is observed by KeyFrames among those nearest to it along the trajectory.
+    Without it a KeyFrame far from a point sees it outside the image, where u - bf / z can be negative: such a drawn
+    stereo observation carries u_right < 0 and is a monocular edge for the optimiser, so the share of stereo edges
+    of a long window falls below stereo_frac (read it from u_right >= 0).  id_order: how mnId relates to list order
+    ("ascending", "descending", "shuffled").  The fixed KeyFrames have the lower ids, KeyFrame id 0 among them when
+    n_fixed > 0.  Returns the problem dict with the truth under "true_Tcw" [K,4,4] float64, "true_pos" [N,3]
+    float64 and "outlier" uint8 [E]."""
+    K = n_free + n_fixed
+    fx, fy, cx, cy = 500.0, 500.0, 320.0, 240.0
+    # truth: camera k at x = 0.3 k, a small yaw, looking down +z
+    Tcw = np.zeros((K, 4, 4))
+    for k in range(K):
+        yaw = 0.02 * (k - K / 2)
+        R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+        c = np.array([0.3 * k, 0.02 * (k % 3), 0.0])
+        Tcw[k, :3, :3] = R
+        Tcw[k, :3, 3] = -R @ c
+        Tcw[k, 3, 3] = 1.0
+    pos = np.stack([rng.uniform(-1.0, 0.3 * K + 1.0, n_points), rng.uniform(-1.0, 1.0, n_points),
+                    rng.uniform(4.0, 9.0, n_points)], axis=1) if n_points else np.zeros((0, 3))
+    ids = np.arange(K, dtype=np.int64) * 3
+    fixed = np.zeros(K, np.uint8)
+    fixed[:n_fixed] = 1
+    mp_id = 7 + 2 * np.arange(n_points, dtype=np.int64)
+    if id_order == "descending":
+        korder, porder = np.arange(K)[::-1], np.arange(n_points)[::-1]
+    elif id_order == "shuffled":
+        korder, porder = rng.permutation(K), rng.permutation(n_points)
+    else:
+        korder, porder = np.arange(K), np.arange(n_points)
+    obs_begin, obs_kf, uv, ur, inv, outl = [0], [], [], [], [], []
+    lo, hi = obs_per_point
+    for p in porder:
+        m = min(K, int(rng.integers(lo, hi + 1)))
+        pool = np.argsort(np.abs(0.3 * np.arange(K) - pos[p, 0]), kind="stable")[:m + 2] if near else K
+        seen = np.sort(rng.choice(pool, size=m, replace=False)) if m else []
+        for k in seen:
+            pc = Tcw[k, :3, :3] @ pos[p] + Tcw[k, :3, 3]
+            u = fx * pc[0] / pc[2] + cx
+            v = fy * pc[1] / pc[2] + cy
+            r = u - bf / pc[2]
+            if noise_px > 0:
+                u, v, r = u + rng.normal(0, noise_px), v + rng.normal(0, noise_px), r + rng.normal(0, noise_px)
+            o = rng.random() < outlier_frac
+            if o:
+                a = rng.uniform(0, 2 * np.pi)
+                u, v, r = u + outlier_px * np.cos(a), v + outlier_px * np.sin(a), r + outlier_px * np.cos(a)
+            st = rng.random() < stereo_frac
+            obs_kf.append(int(np.nonzero(korder == k)[0][0]))
+            uv.append((u, v))
+            ur.append(r if st else -1.0)
+            inv.append(1.0 / 1.2 ** (2 * int(rng.integers(0, 4))))
+            outl.append(1 if o else 0)
+        obs_begin.append(len(obs_kf))
+    # entry estimates: the free poses and the points perturbed
+    T0 = Tcw.copy()
+    for k in range(n_fixed, K):
+        if pose_perturb > 0:
+            w = rng.normal(0, pose_perturb, 3)
+            th = np.linalg.norm(w)
+            Wx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+            dR = np.eye(3) + (np.sin(th) / th) * Wx + ((1 - np.cos(th)) / th ** 2) * Wx @ Wx if th > 0 else np.eye(3)
+            T0[k, :3, :3] = dR @ Tcw[k, :3, :3]
+            T0[k, :3, 3] = dR @ Tcw[k, :3, 3] + rng.normal(0, pose_perturb, 3)
+    p0 = pos + (rng.normal(0, point_perturb, pos.shape) if point_perturb > 0 else 0.0)
+    cam = np.tile(np.array([fx, fy, cx, cy, bf], np.float32), (K, 1))
+    return dict(kf_id=ids[korder].copy(), fixed=fixed[korder].copy(),
+                Tcw=T0[korder].reshape(K, 16).astype(np.float32), cam=cam,
+                mp_id=mp_id[porder].copy(), pos=p0[porder].astype(np.float32),
+                bad=np.zeros(n_points, np.uint8), obs_begin=np.asarray(obs_begin, np.int32),
+                obs_kf=np.asarray(obs_kf, np.int32), uv=np.asarray(uv, np.float32).reshape(-1, 2),
+                u_right=np.asarray(ur, np.float32), inv_sigma2=np.asarray(inv, np.float32),
+                true_Tcw=Tcw[korder].copy(), true_pos=pos[porder].copy(), outlier=np.asarray(outl, np.uint8))
