@@ -12,7 +12,8 @@ HDRS = include/rsc.h $(wildcard $(CSRC)/*.h)
 all: $(LIBDIR)/librsc.so $(LIBDIR)/librsc_spin1.so oracle hostemu frameproj_emu kfproj_emu facade_test facade_proj_test \
      facade_loopproj_test facade_voc_test chase_mirror_test bowvoc_emu localproj_emu facade_localproj_test lastproj_emu \
      facade_lastproj_test facade_triang_test arena_test viewimage_test rounds_test seed_window_test triang_emu fusekf_emu facade_fusekf_test ref_dbow2 \
-     mpupdate_emu facade_mpupdate_test stereo_emu facade_stereo_test localba_emu localba_test facade_localba_test
+     mpupdate_emu facade_mpupdate_test stereo_emu facade_stereo_test localba_emu localba_test facade_localba_test \
+     scan_bound_test
 
 include $(CSRC)/objs.mk
 OBJS = $(RSC_OBJS:%=$(LIBDIR)/%.o)
@@ -147,6 +148,20 @@ $(LIBDIR)/seed_window_test_san: $(SEED_WINDOW_DEPS)
 	mkdir -p $(LIBDIR)
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
 
+# TEST-ONLY host programs: the continue rule of the PnP scan's two-segment counting (rsc_scanbound.h) over every
+# (N, PPT, min_inliers, count) (tests/test_cpu_scan_bound.py); the second build runs under the host sanitizers
+scan_bound_test: $(LIBDIR)/scan_bound_test $(LIBDIR)/scan_bound_test_san
+
+SCAN_BOUND_DEPS = tests/cpp/scan_bound_test.cpp $(CSRC)/rsc_scanbound.h $(CSRC)/rsc_core.h
+
+$(LIBDIR)/scan_bound_test: $(SCAN_BOUND_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -o $@ $<
+
+$(LIBDIR)/scan_bound_test_san: $(SCAN_BOUND_DEPS)
+	mkdir -p $(LIBDIR)
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ $<
+
 # TEST-ONLY host program: the sequential LocalBundleAdjustment restatement (tests/localba_emu) on four scenes of
 # its own (tests/test_cpu_localba.py); the second build runs under the host sanitizers
 localba_test: $(LIBDIR)/localba_test $(LIBDIR)/localba_test_san
@@ -209,4 +224,4 @@ clean:
 
 .PHONY: localba_emu localba_test facade_localba_test
 .PHONY: all oracle ref_dbow2 hostemu frameproj_emu kfproj_emu bowvoc_emu localproj_emu lastproj_emu triang_emu fusekf_emu mpupdate_emu stereo_emu facade_stereo_test facade_mpupdate_test facade_fusekf_test facade_localproj_test facade_lastproj_test facade_triang_test facade_test facade_proj_test facade_loopproj_test \
-        facade_voc_test chase_mirror_test arena_test viewimage_test rounds_test seed_window_test clean
+        facade_voc_test chase_mirror_test arena_test viewimage_test rounds_test seed_window_test scan_bound_test clean

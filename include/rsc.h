@@ -74,6 +74,12 @@ int rsc_context_set_eig_split(rsc_context* ctx, int on);
  * of more than 64 solvers, and rounds with a solver whose rand() window has moved off its seed (or
  * that is bound to a shared stream), take the blob path whatever the setting. */
 int rsc_context_set_round_args(rsc_context* ctx, int on);
+/* PnP inlier scan (no effect on results): 1 (default; env RSC_SCAN_BOUND) a hypothesis that can no
+ * longer reach mRansacMinInliers after the first half of the scan thread's point slices (the first
+ * min(N, 128 PPT) correspondences) is not tested against the rest, and its stored count is the count
+ * so far, which is below mRansacMinInliers; iterate() only ever tests a count against that bound
+ * (PnPsolver.cpp:147).  0: every hypothesis is counted over all correspondences. */
+int rsc_context_set_scan_bound(rsc_context* ctx, int on);
 /* Diagnostic: PnP speculation rounds of the context so far on [0] the argument path, [1] the blob
  * path, and [2] uploads of the resident problem table. */
 int rsc_diag_round_paths(rsc_context* ctx, int64_t out[3]);
@@ -148,8 +154,21 @@ int rsc_pnp_get_state(const rsc_pnp* s, int32_t out[8]);
 int rsc_pnp_last_samples(rsc_pnp* s, int32_t* out, int cap);
 /* Parity hook: inlier counts and float poses (R row-major 9 + t 3) of every hypothesis of the last
  * launch for this solver (PnPsolver.cpp:139-146 mnInliersi / mRi, mti per hypothesis).  Valid until
- * the context's next launch. */
+ * the context's next launch.  The counts are always the full counts: when that launch ran with the
+ * scan bound on (rsc_context_set_scan_bound), the first call that asks for counts runs the launch's
+ * scan once more with the bound off, on the same tables, records and outputs, and waits for it; later
+ * calls find the round already recounted.  Lifetime: the context's buffers that launch reads stay valid
+ * until the context's next launch of any kind, but it also reads the correspondences of every solver
+ * of the round, which go with the solver.  So the recount needs all PnP solvers of the context alive:
+ * once one has been destroyed after a round that still awaits its recount, a call that asks for counts
+ * launches nothing and returns RSC_ERR_UNSUPPORTED, for every solver of that round, until the context's
+ * next launch (rsc_pnp_last_counts_raw still returns what the round left; poses alone, counts == NULL,
+ * are still served). */
 int rsc_pnp_last_hypotheses(rsc_pnp* s, int32_t* counts, float* poses, int cap);
+/* The counts of the last launch for this solver as they stand in the count buffer: before a recount by
+ * rsc_pnp_last_hypotheses, what the round itself left (a hypothesis cut short by the scan bound shows
+ * its count over the first min(N, 128 PPT) correspondences).  Returns the number written. */
+int rsc_pnp_last_counts_raw(rsc_pnp* s, int32_t* counts, int cap);
 
 /* ---- Sim3Solver (include/Sim3Solver.hpp:16-103, src/Sim3Solver.cpp) --------------------------- */
 /* Raw constructor inputs for one keyframe pair (Sim3Solver.cpp:6-85), per match slot i1 < n1. */

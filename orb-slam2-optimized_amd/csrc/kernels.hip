@@ -4,9 +4,11 @@
 //                          in two stages: lane pairs per hypothesis for the 12x12 eigenvectors,
 //                          then one wave per (beta approximation, 64 hypotheses) (rsc_quad.h).
 //   pnp_scan_kernel<PPT>   PnPsolver::CheckInliers for a chunk of hypotheses of one problem:
-//                          256 threads hold the problem's correspondences in VGPRs (PPT per
-//                          thread); per hypothesis every lane tests its points, __ballot gives the
-//                          64-bit inlier words, popcount gives the count.
+//                          256 threads hold one segment of the problem's correspondences in VGPRs
+//                          (PPT per thread in two segments); per hypothesis every lane tests its
+//                          points, __ballot gives the 64-bit inlier words, popcount gives the count;
+//                          a hypothesis that cannot reach mRansacMinInliers after the first segment
+//                          is not counted over the second (rsc_scanbound.h).
 //   pnp_refine_kernel      PnPsolver::Refine: compaction of the best inlier set into the grow-only
 //                          EPnP buffers, EPnP over n_r rows (MtM built block-parallel), then the
 //                          block-parallel CheckInliers of the refined pose.
@@ -66,6 +68,7 @@ __device__ uint64_t g_solve_stamps[3][4096][8];
 #include "rsc_quad.h"
 #include "rsc_math.h"
 #include "rsc_kernels.h"
+#include "rsc_scanbound.h"
 
 namespace rsc {
 
@@ -126,20 +129,28 @@ __global__ __launch_bounds__(64) void pnp_betas_kernel(const DevPnP* __restrict_
 //     tools/rcp_exhaustive.hip); the compiler's IEEE division is the same core wrapped in range
 //     scaling and special-value fix-ups (10 instructions per point instead of 2).  `ok` is cleared
 //     for a point outside that range (0, denormals, huge, inf, NaN), and the caller then redoes the
-//     hypothesis with pnp_inlier.
+//     hypothesis with the IEEE division (kFast = false below: pnp_inlier's arithmetic).
 // The projection stays scalar double as the reference's (:253).
+// kFast = false: the same packed arithmetic around the IEEE division 1.0f / Zc (the redo of such a
+// hypothesis on the registers the fast form reads; `ok` is left alone).
 typedef float rsc_f2 __attribute__((ext_vector_type(2)));
+template <bool kFast = true>
 __device__ __forceinline__ void pnp_inlier2(const float (&R)[9], const float (&t)[3], double fx, double fy, double cx,
                                             double cy, rsc_f2 X, rsc_f2 Y, rsc_f2 Z, rsc_f2 u, rsc_f2 v, rsc_f2 maxErr,
                                             bool& in0, bool& in1, bool& ok) {
     const rsc_f2 Xc = (R[0] * X + (R[1] * Y + R[2] * Z)) + t[0];  // ered3, then + mti
     const rsc_f2 Yc = (R[3] * X + (R[4] * Y + R[5] * Z)) + t[1];
     const rsc_f2 Zc = (R[6] * X + (R[7] * Y + R[8] * Z)) + t[2];
-    const rsc_f2 r0 = {__builtin_amdgcn_rcpf(Zc.x), __builtin_amdgcn_rcpf(Zc.y)};
-    const rsc_f2 e = __builtin_elementwise_fma(-Zc, r0, (rsc_f2){1.0f, 1.0f});
-    const rsc_f2 iz = __builtin_elementwise_fma(e, r0, r0);
-    const float a0 = fabsf(Zc.x), a1 = fabsf(Zc.y);
-    ok = ok & (a0 >= 0x1p-126f) & (a0 <= 0x1p125f) & (a1 >= 0x1p-126f) & (a1 <= 0x1p125f);
+    rsc_f2 iz;
+    if constexpr (kFast) {
+        const rsc_f2 r0 = {__builtin_amdgcn_rcpf(Zc.x), __builtin_amdgcn_rcpf(Zc.y)};
+        const rsc_f2 e = __builtin_elementwise_fma(-Zc, r0, (rsc_f2){1.0f, 1.0f});
+        iz = __builtin_elementwise_fma(e, r0, r0);
+        const float a0 = fabsf(Zc.x), a1 = fabsf(Zc.y);
+        ok = ok & (a0 >= 0x1p-126f) & (a0 <= 0x1p125f) & (a1 >= 0x1p-126f) & (a1 <= 0x1p125f);
+    } else {
+        iz = (rsc_f2){1.0f / Zc.x, 1.0f / Zc.y};
+    }
     const rsc_f2 ue = {(float)(cx + fx * (double)Xc.x * (double)iz.x), (float)(cx + fx * (double)Xc.y * (double)iz.y)};
     const rsc_f2 ve = {(float)(cy + fy * (double)Yc.x * (double)iz.x), (float)(cy + fy * (double)Yc.y * (double)iz.y)};
     const rsc_f2 du = ue - u, dv = ve - v;
@@ -158,20 +169,26 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
                                                        int32_t* __restrict__ counts,
                                                        int32_t* __restrict__ counts_dev,
                                                        uint64_t* __restrict__ masks, int mask_words,
-                                                       int32_t* __restrict__ qual, const A args) {
-    // Hypotheses per flush: the 4 waves' counts of a batch wait in LDS until the batch's totals are
-    // summed.  The only inlier mask of a round's problem that is ever read is the one of its FIRST
+                                                       int32_t* __restrict__ qual, int bound, const A args) {
+    // The only inlier mask of a round's problem that is ever read is the one of its FIRST
     // hypothesis reaching mRansacMinInliers: the replay pauses there (rsc_engine.h
     // pnp_iterate_many: pause_k, adopted if it beats the best), pnp_select_refine_kernel selects the
     // same one, the Refine reads it, and after the Refine the solver is done or the rest of the
-    // round is speculated again (PnPsolver.cpp:176-195).  So the loop keeps no mask words: the
-    // flushes note the chunk's first qualifying hypothesis — the problem's first is the first of
-    // its chunk — and its ballots are taken a second time after the chunk is counted (ballots()
-    // below, the same code on the same pose record) and stored.  In exhaustive relocalization
-    // batches none qualifies, and the loop pays nothing for the masks.
-    constexpr int B = PPT <= 8 ? 64 : 512 / PPT;
-    __shared__ int wave_cnt[4][B];
-    __shared__ int first_sh;  // the chunk's first qualifying hypothesis, -1: none (set by every flush)
+    // round is speculated again (PnPsolver.cpp:176-195).  So the counting keeps no mask words: the
+    // chunk's first qualifying hypothesis — the problem's first is the first of its chunk — has
+    // its ballots taken a second time after the chunk is counted (ballots() below, the same code on
+    // the same pose record) and stored.  In exhaustive relocalization batches none qualifies, and
+    // the loop pays nothing for the masks.
+    //
+    // Likewise a count is only ever tested against mRansacMinInliers (rsc_scanbound.h), so for
+    // PPT >= 2 the thread's slices form two segments: A = slices [0, PPT/2), the first
+    // kA = min(N, 128 PPT) points, and B the rest.  Every hypothesis is counted over A; only those
+    // that can still reach min_inliers (scan_continue; all with points in B when `bound` is 0) are
+    // counted over B.  The stored count of the others is their count over A, which is below
+    // min_inliers.  One segment's points are resident in VGPRs at a time.
+    constexpr int NSEG = PPT >= 2 ? 2 : 1;
+    constexpr int SPT = PPT / NSEG;  // slices of a segment
+    __shared__ int wave_cnt[4][64];  // the 4 waves' counts of the chunk's hypotheses over the resident segment
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int4 wt = wg_table[blockIdx.x];
     const auto& lp = round_rec(lps, args, wt.x);
@@ -189,17 +206,40 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
         e1 = berr[hcap + rec0 + lane];
         e2 = berr[2 * hcap + rec0 + lane];
     }
-    float X[PPT], Y[PPT], Z[PPT], U[PPT], V[PPT], E[PPT];
-    RSC_UNROLL for (int s = 0; s < PPT; ++s) {
-        const int i = s * 256 + tid;
-        if (i < P.n) {
-            const float4 p = P.pts[i];
-            const float2 q = P.uv[i];
-            X[s] = p.x; Y[s] = p.y; Z[s] = p.z; E[s] = p.w * P.th2; U[s] = q.x; V[s] = q.y;  // mvMaxError (:91-93)
-        } else {
-            X[s] = 0.f; Y[s] = 0.f; Z[s] = 1.f; E[s] = -1.f; U[s] = 0.f; V[s] = 0.f;  // never an inlier
+    // the resident segment's points: slice s of segment g is points 256 (g SPT + s) + tid, kept as
+    // the register pairs the packed arithmetic reads (slices 2 k and 2 k + 1 in pair k).  The loads
+    // of all slices are issued before the first is used (a lane past the end reads the problem's
+    // last point and discards it); the pointers are read where they are used, so they hold no
+    // scalar registers through the hypothesis loop.
+    constexpr int NP = (SPT + 1) / 2;
+    rsc_f2 X[NP], Y[NP], Z[NP], U[NP], V[NP], E[NP];
+    auto load_segment = [&](int g) {
+        const int n = P.n;
+        const float4* __restrict__ pts = P.pts;
+        const float2* __restrict__ uv = P.uv;
+        const float th2 = P.th2;
+        float4 p[SPT] = {};
+        float2 q[SPT] = {};
+        if (n > 0) {
+            RSC_UNROLL for (int s = 0; s < SPT; ++s) {
+                const int ic = min((g * SPT + s) * 256 + tid, n - 1);
+                p[s] = pts[ic];
+                q[s] = uv[ic];
+            }
         }
-    }
+        RSC_UNROLL for (int s = 0; s < SPT; ++s) {
+            const bool in = (g * SPT + s) * 256 + tid < n;
+            X[s >> 1][s & 1] = in ? p[s].x : 0.f;
+            Y[s >> 1][s & 1] = in ? p[s].y : 0.f;
+            Z[s >> 1][s & 1] = in ? p[s].z : 1.f;
+            E[s >> 1][s & 1] = in ? p[s].w * th2 : -1.f;  // mvMaxError (:91-93); past the end: never an inlier
+            U[s >> 1][s & 1] = in ? q[s].x : 0.f;
+            V[s >> 1][s & 1] = in ? q[s].y : 0.f;
+        }
+        if constexpr (SPT == 1) {  // a one-slice segment: the point in both halves
+            X[0].y = X[0].x; Y[0].y = Y[0].x; Z[0].y = Z[0].x; E[0].y = E[0].x; U[0].y = U[0].x; V[0].y = V[0].x;
+        }
+    };
     int best = 0;
     {
         double be = e0;
@@ -211,45 +251,49 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
         const size_t apx = (size_t)((pick1 >> j) & 1u) + 2 * (size_t)((pick2 >> j) & 1u);
         return bpose + (apx * hcap + rec0 + (size_t)j) * 12;
     };
-    // the selected poses go to `poses` (the select / refine kernels, the gather and the parity
-    // hooks read them there): every hypothesis belongs to exactly one scan workgroup
-    for (int w = tid; w < wt.z * 12; w += 256) {
-        const int hj = w / 12, k = w - 12 * hj;
-        poses[(rec0 + hj) * 12 + k] = pose_of(hj)[k];
-    }
-    // The wave's PPT inlier words of one pose.  The PPT points of a lane are independent: all
-    // ballots are taken before anything is done with them, so the compiler can interleave the
-    // points' arithmetic.  The counting pass and the mask pass both go through here.
-    auto ballots = [&](const float (&R)[9], const float (&t)[3], uint64_t (&b)[PPT]) {
+    // The wave's SPT inlier words of one pose over the resident segment.  The points of a lane are
+    // independent: all ballots are taken before anything is done with them, so the compiler can
+    // interleave the points' arithmetic.  The counting steps and the mask steps all go through here.
+    auto ballots = [&](const float (&R)[9], const float (&t)[3], uint64_t (&b)[SPT]) {
         if constexpr (PPT >= 2) {
             bool ok = true;
-            RSC_UNROLL for (int s = 0; s < PPT; s += 2) {
+            RSC_UNROLL for (int k = 0; k < NP; ++k) {
                 bool i0, i1;
-                pnp_inlier2(R, t, fx, fy, cx, cy, (rsc_f2){X[s], X[s + 1]}, (rsc_f2){Y[s], Y[s + 1]},
-                            (rsc_f2){Z[s], Z[s + 1]}, (rsc_f2){U[s], U[s + 1]}, (rsc_f2){V[s], V[s + 1]},
-                            (rsc_f2){E[s], E[s + 1]}, i0, i1, ok);
-                b[s] = __ballot(i0);
-                b[s + 1] = __ballot(i1);
+                pnp_inlier2(R, t, fx, fy, cx, cy, X[k], Y[k], Z[k], U[k], V[k], E[k], i0, i1, ok);
+                b[2 * k] = __ballot(i0);
+                if (2 * k + 1 < SPT) b[2 * k + 1] = __ballot(i1);
             }
             // a depth outside the fast reciprocal's range on any lane (a point on the camera
-            // plane, a degenerate pose): the whole hypothesis again with the IEEE division
+            // plane, a degenerate pose): the hypothesis' segment again with the IEEE division
             if (__builtin_expect(__any(!ok), 0)) {
-                RSC_UNROLL for (int s = 0; s < PPT; ++s)
-                    b[s] = __ballot(pnp_inlier(R, t, fx, fy, cx, cy, X[s], Y[s], Z[s], U[s], V[s], E[s]));
+                RSC_UNROLL for (int k = 0; k < NP; ++k) {
+                    bool i0, i1;
+                    pnp_inlier2<false>(R, t, fx, fy, cx, cy, X[k], Y[k], Z[k], U[k], V[k], E[k], i0, i1, ok);
+                    b[2 * k] = __ballot(i0);
+                    if (2 * k + 1 < SPT) b[2 * k + 1] = __ballot(i1);
+                }
             }
         } else {
-            RSC_UNROLL for (int s = 0; s < PPT; ++s)
-                b[s] = __ballot(pnp_inlier(R, t, fx, fy, cx, cy, X[s], Y[s], Z[s], U[s], V[s], E[s]));
+            b[0] = __ballot(pnp_inlier(R, t, fx, fy, cx, cy, X[0].x, Y[0].x, Z[0].x, U[0].x, V[0].x, E[0].x));
         }
     };
-    // Two passes through ONE loop body (a second copy of ballots() in the kernel costs registers:
-    // 104 VGPRs instead of at most 96 at PPT 8, a workgroup per CU less).  Pass 0 takes every
-    // hypothesis of the chunk and counts; pass 1 takes the chunk's first qualifying one again and
-    // stores its mask words.  `todo` holds the pass' hypotheses as bits (scalar); the next pose is
-    // loaded before the current one is used.
+    // 2 NSEG steps through ONE loop body and ONE load site (a second copy of ballots() in the kernel
+    // costs registers).  Step 0 counts every hypothesis of the chunk over segment A;
+    // step 1 (NSEG == 2) counts the hypotheses of `cont` over B; then the chunk's first qualifying
+    // hypothesis is taken again and its mask words stored, first those of the resident segment,
+    // then (NSEG == 2) those of the other one.  `todo` holds the step's hypotheses as bits
+    // (scalar); the next pose is loaded before the current one is used.  Every wave sums the chunk's
+    // totals for itself (lane j: hypothesis j), so `cont` and the first qualifier are wave masks
+    // in scalar registers and need no broadcast; wave 0 writes the counts.
     uint64_t todo = wt.z >= 64 ? ~0ull : (1ull << wt.z) - 1;
-    int first = -1;  // wave 0: the chunk's first qualifying hypothesis so far
-    for (int pass = 0; pass < 2; ++pass) {
+    uint64_t cont = 0;  // hypotheses counted over B
+    int first = -1;     // the chunk's first qualifying hypothesis, -1: none (or no masks wanted)
+    int c = 0;          // lane j: hypothesis j's count so far
+    _Pragma("nounroll") for (int step = 0; step < 2 * NSEG; ++step) {
+        const bool store = step >= NSEG;
+        // the step's segment: A, B, then the resident one (B if any hypothesis went on) and the other
+        const int seg = NSEG == 1 ? 0 : (step == 1) | (step == 2 && cont) | (step == 3 && !cont);
+        if (todo && step != NSEG) load_segment(seg);
         float Rn[9] = {}, tn[3] = {};
         if (todo) {
             const float* pp = pose_of(__ffsll((unsigned long long)todo) - 1);
@@ -267,45 +311,53 @@ __global__ __launch_bounds__(256) void pnp_scan_kernel(const DevPnP* __restrict_
                 RSC_UNROLL for (int k = 0; k < 9; ++k) Rn[k] = pp[k];
                 RSC_UNROLL for (int k = 0; k < 3; ++k) tn[k] = pp[9 + k];
             }
-            uint64_t b[PPT];
+            uint64_t b[SPT];
             ballots(R, t, b);
-            if (pass == 1) {
+            if (store) {
                 // word 4 s + wave of the hypothesis' mask row = points 256 s + 64 wave + lane
                 if (lane == 0) {
-                    uint64_t* row = masks + (rec0 + (size_t)j) * mask_words;
-                    RSC_UNROLL for (int s = 0; s < PPT; ++s) row[4 * s + wave] = b[s];
+                    uint64_t* row = masks + (rec0 + (size_t)j) * mask_words + 4 * SPT * seg;
+                    RSC_UNROLL for (int s = 0; s < SPT; ++s) row[4 * s + wave] = b[s];
                 }
                 continue;
             }
             int cnt = 0;
-            RSC_UNROLL for (int s = 0; s < PPT; ++s) cnt += __popcll(b[s]);
-            const int jb = j % B;
-            if (lane == 0) wave_cnt[wave][jb] = cnt;
-            if (jb == B - 1 || !todo) {
-                __syncthreads();
-                const int base = j - jb;
-                bool q = false;
-                if (tid <= jb) {
-                    const int c = wave_cnt[0][tid] + wave_cnt[1][tid] + wave_cnt[2][tid] + wave_cnt[3][tid];
-                    counts[lp.out0 + wt.y + base + tid] = c;
-                    if (counts_dev) counts_dev[lp.out0 + wt.y + base + tid] = c;  // pnp_select_refine_kernel
-                    // the problem has a hypothesis reaching mRansacMinInliers: the host replay reads its
-                    // counts (it skips the counts of a problem without one, rsc_engine.h)
-                    q = c >= lp.min_inliers;
-                    if (q) qual[wt.x] = 1;
-                }
-                // jb < B <= 64: the batch's totals are all in wave 0, whose ballot is the batch's
-                // qualifiers (the other waves see none and do not write)
-                const uint64_t qb = __ballot(q);
-                if (first < 0 && qb) first = base + __ffsll((unsigned long long)qb) - 1;
-                if (tid == 0) first_sh = first;
-                __syncthreads();  // the totals are read (the next batch overwrites wave_cnt); first_sh is set
+            RSC_UNROLL for (int s = 0; s < SPT; ++s) cnt += __popcll(b[s]);
+            if (lane == 0) wave_cnt[wave][j] = cnt;
+        }
+        if (step == 0 || (step < NSEG && cont)) {
+            // the chunk's totals over the segment just counted (a block-uniform branch)
+            __syncthreads();
+            if (lane < wt.z && (step == 0 || ((cont >> lane) & 1)))
+                c += wave_cnt[0][lane] + wave_cnt[1][lane] + wave_cnt[2][lane] + wave_cnt[3][lane];
+            if (step + 1 < NSEG) {
+                const int n = P.n;
+                cont = __ballot(lane < wt.z && scan_continue(n, scan_seg_a_points(n, PPT), c, lp.min_inliers, bound != 0));
+                __syncthreads();  // the totals are read: step 1 overwrites wave_cnt
+                todo = cont;
             }
         }
-        if (pass == 0 && masks && wt.z > 0) {
-            const int f = __builtin_amdgcn_readfirstlane(first_sh);
-            if (f >= 0) todo = 1ull << f;
+        if (step == NSEG - 1) {
+            // final counts: exact, or (not in cont, N > kA) the count over A, which is below min_inliers
+            const bool q = lane < wt.z && c >= lp.min_inliers;
+            if (wave == 0 && lane < wt.z) {
+                counts[lp.out0 + wt.y + lane] = c;
+                if (counts_dev) counts_dev[lp.out0 + wt.y + lane] = c;  // pnp_select_refine_kernel
+                // the problem has a hypothesis reaching mRansacMinInliers: the host replay reads its
+                // counts (it skips the counts of a problem without one, rsc_engine.h)
+                if (q) qual[wt.x] = 1;
+            }
+            const uint64_t qb = __ballot(q);
+            if (masks && qb) first = __ffsll((unsigned long long)qb) - 1;
         }
+        if (store || step == NSEG - 1) todo = first >= 0 ? 1ull << first : 0;  // its mask words, segment by segment
+    }
+    // the selected poses go to `poses` (the select / refine kernels, the gather and the parity
+    // hooks read them there): every hypothesis belongs to exactly one scan workgroup.  After the
+    // loop: inside it the per-lane addresses would be held in registers through every step.
+    for (int w = tid; w < wt.z * 12; w += 256) {
+        const int hj = w / 12, k = w - 12 * hj;
+        poses[(rec0 + hj) * 12 + k] = pose_of(hj)[k];
     }
 }
 
@@ -1367,17 +1419,17 @@ hipError_t launch_selftest_math(int fn, const double* x, int n, double* out, hip
 
 hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const RoundArgs* args,
                            const int4* wgt, const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev,
-                           uint64_t* masks, int mask_words, int32_t* qual, hipStream_t st) {
+                           uint64_t* masks, int mask_words, int32_t* qual, bool bound, hipStream_t st) {
     if (!lps && !args) return hipErrorInvalidValue;
     switch (ppt) {
 #define RSC_CASE(P)                                                                                                  \
     case P:                                                                                                          \
         if (args)                                                                                                    \
             pnp_scan_kernel<P, RoundArgs><<<nwg, 256, 0, st>>>(probs, nullptr, wgt, bs.err, bs.pose, bs.hcap, poses, \
-                                                               counts, counts_dev, masks, mask_words, qual, *args); \
+                                                               counts, counts_dev, masks, mask_words, qual, bound, *args); \
         else                                                                                                         \
             pnp_scan_kernel<P, NoRoundArgs><<<nwg, 256, 0, st>>>(probs, lps, wgt, bs.err, bs.pose, bs.hcap, poses,   \
-                                                                 counts, counts_dev, masks, mask_words, qual,       \
+                                                                 counts, counts_dev, masks, mask_words, qual, bound,\
                                                                  NoRoundArgs{});                                    \
         break;
         RSC_CASE(1) RSC_CASE(2) RSC_CASE(4) RSC_CASE(8) RSC_CASE(16) RSC_CASE(32)

@@ -92,17 +92,19 @@ bool scan_wgs_overridden() {
 
 // Scan workgroups of a PnP round: chunks[i] even chunks for problem i's H[i] hypotheses (sizes
 // differ by at most one, even_chunk below).  `capacity` is what the device holds at once
-// (pnp_scan_kernel<PPT>'s workgroups per CU x CUs) and `batch` the kernel's batch B (hypotheses per flush).
+// (pnp_scan_kernel<PPT>'s workgroups per CU x CUs) and `batch` the most hypotheses a workgroup takes
+// (kScanMaxChunk: lane j of a wave stands for the chunk's hypothesis j).
 //   * The round gets k x capacity workgroups, dealt to the problems in proportion to their
-//     hypotheses, with the smallest k whose chunks fit one batch: whole rounds of residency, so
+//     hypotheses, with the smallest k whose chunks stay within `batch`: whole rounds of residency, so
 //     no CU idles through a part-filled last round, and each workgroup's head (table -> launch
 //     record -> problem -> points) is paid for as many hypotheses as a full device allows
-//     (config 2: 1,280 x 15 instead of 2,432 x 8 or 4).
+//     (config 2: 1,792 x 10 or 11 instead of 2,432 x 8 or 4).
 //   * Never fewer than kScanMinChunk hypotheses per point load, so a round too small to fill the
 //     device (the single event) keeps ceil(H / 8) workgroups per problem: it is latency-bound and
 //     wants the width.
 // Placement only: the counts, masks and poses do not depend on it.
 constexpr int kScanMinChunk = 8;
+constexpr int kScanMaxChunk = 64;
 void pnp_scan_partition(const int* H, int count, int capacity, int batch, std::vector<int>& chunks) {
     chunks.assign((size_t)count, 1);
     int64_t total = 0;
@@ -201,6 +203,7 @@ int upload_blob(rsc_context* C, const Blob& b) {
 // Inlier counts of a speculation round: written by the scan kernel straight into pinned host
 // memory (one fewer copy and no blit launch before the host replay), or into HBM + a D2H copy.
 int counts_target(rsc_context* C, int total, int32_t** dst) {
+    C->pnp_scan_last.forget();  // the count buffer gets a new round (the speculate()s did this on entry)
     if (int e = C->h_counts.ensure((size_t)total)) return e;
     if (C->direct_counts) {
         *dst = C->h_counts.p;
@@ -264,6 +267,8 @@ struct HipPnPBackend : PnPBackend {
     }
 
     int speculate(PnPState* const* S, int count, const int* H, std::vector<std::vector<int32_t>>& counts) override {
+        // before anything the last round's scan reads (tables, problem table, buffers) can change
+        C->pnp_scan_last.forget();
         // group by min_set (template parameter of the solve kernel)
         int total = 0, maxN = 1;
         // per-thread scratch that keeps its capacity across rounds (no allocation per round)
@@ -361,7 +366,10 @@ struct HipPnPBackend : PnPBackend {
             }
             scan_cap = C->pnp_scan_capacity[lg];
         }
-        const int scan_batch = ppt <= 8 ? 64 : 512 / ppt;  // pnp_scan_kernel's B
+        // The chunk limit is the kernel's, 64 for every PPT.  (Before the two-segment kernel the counts
+        // were flushed in batches of 512 / PPT for PPT 16 and 32 and the chunks were capped there;
+        // the partition differs only for rounds beyond 512 / PPT x capacity hypotheses.)
+        const int scan_batch = kScanMaxChunk;
         const int hb = (total <= kEigHyps * C->eig_rows_max_wgs) ? C->betas_small_hb : kBetasHyps;
 
         // The tables depend only on the round's shape (count, sample size and H per problem, the scan's
@@ -375,7 +383,6 @@ struct HipPnPBackend : PnPBackend {
         key.push_back(count);
         key.push_back(HC);
         key.push_back(scan_cap);
-        key.push_back(scan_batch);
         key.push_back(hb);
         for (int i = 0; i < count; ++i) {
             key.push_back(S[i]->mRansacMinSet);
@@ -481,7 +488,7 @@ struct HipPnPBackend : PnPBackend {
             if (int e = C->h_selout.ensure((size_t)count)) return e;
         }
         // of a round's mask rows only the one of each scan chunk's first qualifying hypothesis is
-        // written (pnp_scan_kernel, pass 1); every other row holds what earlier rounds left
+        // written (pnp_scan_kernel's storing steps); every other row holds what earlier rounds left
         if (int e = C->d_masks.ensure((size_t)total * mw)) return e;
         if (int e = C->d_samples.ensure((size_t)total * 8)) return e;
         if (int e = C->d_stage.ensure((size_t)total * kStageDoubles)) return e;
@@ -507,8 +514,28 @@ struct HipPnPBackend : PnPBackend {
         timing_begin(C, 1);
         RSC_HIP(launch_pnp_scan(ppt, (int)scan_wgs.size(), dprobs, dlps, dargs,
                                 reinterpret_cast<const int4*>(tab + C->pnp_tab_scan),
-                                bs, C->d_poses.p, cnt_dst, cnt_dev, C->d_masks.p, mw, C->h_qual.p, C->stream));
+                                bs, C->d_poses.p, cnt_dst, cnt_dev, C->d_masks.p, mw, C->h_qual.p, C->scan_bound,
+                                C->stream));
         timing_begin(C, 2);
+        if (C->scan_bound) {
+            // what rsc_pnp_last_hypotheses needs to count this round again in full (pnp_recount)
+            rsc_context::PnpScanLaunch& L = C->pnp_scan_last;
+            L.use_args = use_args;
+            L.ppt = ppt;
+            L.nwg = (int)scan_wgs.size();
+            L.mask_words = mw;
+            L.total = total;
+            L.counts = cnt_dst;
+            L.counts_dev = cnt_dev;
+            if (use_args) {
+                std::memcpy(L.args.r, ra.r, sizeof(RoundRec) * (size_t)count);
+            } else {
+                L.probs.assign(probs.begin(), probs.end());
+                L.lps.assign(lps.begin(), lps.end());
+            }
+            L.destroyed = C->pnp_destroyed->load(std::memory_order_relaxed);
+            L.pending = true;
+        }
         if (fused) {
             timing_begin(C, 3);
             RSC_HIP(launch_pnp_select_refine(count, dprobs, dsels, use_args ? &sa : nullptr,
@@ -689,6 +716,7 @@ struct HipSim3Backend : Sim3Backend {
     std::vector<rsc_sim3*> all;
 
     int speculate(Sim3State* const* S, int count, const int* H, std::vector<std::vector<int32_t>>& counts) override {
+        C->pnp_scan_last.forget();  // this round reuses the PnP round's pose, mask and count buffers
         pick_valid = false;  // set again only once this round's pick kernel is enqueued
         int total = 0, maxN = 1;
         // per-thread scratch that keeps its capacity across rounds (no allocation per round)
@@ -857,6 +885,7 @@ struct HipMLBackend : MLBackend {
     }
 
     int speculate(MLState* const* S, int count, const int* H, std::vector<std::vector<int32_t>>& counts) override {
+        C->pnp_scan_last.forget();  // this round reuses the PnP round's mask and count buffers
         int total = 0, maxN = 1;
         std::vector<DevML> probs(count);
         std::vector<LaunchProb> lps(count);
@@ -1042,6 +1071,48 @@ static int bound_iterate_many(Solver* const* solvers, int count, const int32_t* 
     return RSC_OK;
 }
 
+// The context's last PnP round counted again with the scan bound off, once: the same tables, records,
+// betas results and outputs as the round's own scan launch (all valid until the context's next
+// speculation), so the counts become exact and qual, the first qualifiers' masks and the poses are
+// written again with the values the replay already used.
+namespace {
+int pnp_recount(rsc_context* C) {
+    rsc_context::PnpScanLaunch& L = C->pnp_scan_last;
+    // The problem table names every solver's point buffers: after a PnP solver of the context has been
+    // destroyed the launch could read freed memory, so the round stays as it is.
+    if (L.pending && L.destroyed != C->pnp_destroyed->load(std::memory_order_relaxed)) {
+        L.pending = false;
+        L.lost = true;
+    }
+    if (L.lost) {
+        g_last_error = "a PnP solver of the context was destroyed after its last round: that round's full counts "
+                       "are gone (rsc_pnp_last_counts_raw returns what the round left)";
+        return RSC_ERR_UNSUPPORTED;
+    }
+    if (!L.pending) return 0;
+    RSC_HIP(hipSetDevice(C->device));
+    const DevPnP* dprobs = C->d_pnp_probs.p;
+    const LaunchProb* dlps = nullptr;
+    if (!L.use_args) {
+        Blob b;
+        const size_t o_probs = b.add(L.probs.data(), L.probs.size() * sizeof(DevPnP));
+        const size_t o_lps = b.add(L.lps.data(), L.lps.size() * sizeof(LaunchProb));
+        if (int e = upload_blob(C, b)) return e;
+        dprobs = reinterpret_cast<const DevPnP*>(C->d_desc.p + o_probs);
+        dlps = reinterpret_cast<const LaunchProb*>(C->d_desc.p + o_lps);
+    }
+    const BetasScratch bs{C->d_berr.p, C->d_bpose.p, (size_t)L.total};
+    RSC_HIP(launch_pnp_scan(L.ppt, L.nwg, dprobs, dlps, L.use_args ? &L.args : nullptr,
+                            reinterpret_cast<const int4*>(C->d_pnp_tab.p + C->pnp_tab_scan), bs, C->d_poses.p, L.counts,
+                            L.counts_dev, C->d_masks.p, L.mask_words, C->h_qual.p, false, C->stream));
+    if (L.counts != C->h_counts.p)
+        RSC_HIP(hipMemcpyAsync(C->h_counts.p, L.counts, (size_t)L.total * 4, hipMemcpyDeviceToHost, C->stream));
+    RSC_HIP(hipStreamSynchronize(C->stream));
+    L.pending = false;
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int rsc_version(void) { return 1; }
@@ -1071,6 +1142,7 @@ int rsc_context_create(int device, rsc_context** out) {
     RSC_HIP(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking));
     C->own_stream = true;
     if (const char* m = std::getenv("RSC_DIRECT_COUNTS")) C->direct_counts = std::strcmp(m, "0") != 0;
+    if (const char* m = std::getenv("RSC_SCAN_BOUND")) C->scan_bound = std::strcmp(m, "0") != 0;
     if (const char* m = std::getenv("RSC_FUSED_REFINE")) C->fused_refine = std::strcmp(m, "0") != 0;
     if (const char* m = std::getenv("RSC_DMA_UPLOAD")) C->dma_upload = std::strcmp(m, "0") != 0;
     if (const char* m = std::getenv("RSC_EIG_ROWS")) C->eig_rows_max_wgs = std::max(0, std::atoi(m));
@@ -1140,6 +1212,12 @@ int rsc_context_set_eig_split(rsc_context* C, int on) {
 int rsc_context_set_round_args(rsc_context* C, int on) {
     if (!C) return RSC_ERR_ARG;
     C->round_args = on != 0;
+    return RSC_OK;
+}
+
+int rsc_context_set_scan_bound(rsc_context* C, int on) {
+    if (!C) return RSC_ERR_ARG;
+    C->scan_bound = on != 0;
     return RSC_OK;
 }
 
@@ -1217,6 +1295,7 @@ int rsc_pnp_create(rsc_context* C, const rsc_pnp_problem* pb, uint32_t seed, rsc
     RSC_HIP(hipSetDevice(C->device));
     std::unique_ptr<rsc_pnp> S(new rsc_pnp());
     S->ctx = C;
+    S->ctx_destroyed = C->pnp_destroyed;
     PnPState& s = S->st;
     s.N = pb->n;
     s.N_points = pb->n_points;
@@ -1257,6 +1336,8 @@ int rsc_pnp_create(rsc_context* C, const rsc_pnp_problem* pb, uint32_t seed, rsc
     return RSC_OK;
 }
 
+// ~rsc_pnp counts the context's pnp_destroyed up: a round that named this solver's buffers is not
+// counted again (pnp_recount)
 void rsc_pnp_destroy(rsc_pnp* s) { delete s; }
 
 int rsc_pnp_set_ransac_parameters(rsc_pnp* s, double probability, int min_inliers, int max_iterations, int min_set,
@@ -1379,7 +1460,15 @@ int last_hypotheses(rsc_context* C, int out0, int H, int stride, int32_t* counts
 
 int rsc_pnp_last_hypotheses(rsc_pnp* s, int32_t* counts, float* poses, int cap) {
     if (!s) return RSC_ERR_ARG;
+    // a round that ran with the scan bound on left partial counts for the hypotheses it cut short
+    if (counts && s->spec_out0 >= 0)
+        if (int e = pnp_recount(s->ctx)) return e;
     return last_hypotheses(s->ctx, s->spec_out0, s->spec_H, 12, counts, poses, cap);
+}
+
+int rsc_pnp_last_counts_raw(rsc_pnp* s, int32_t* counts, int cap) {
+    if (!s || !counts) return RSC_ERR_ARG;
+    return last_hypotheses(s->ctx, s->spec_out0, s->spec_H, 12, counts, nullptr, cap);
 }
 
 // ---- Sim3 ----

@@ -4,7 +4,9 @@
 // structs, RSC_HIP, the buffers, and the staging helpers of the batched calls.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <chrono>
+#include <memory>
 #include <string>
 #include "../../include/rsc.h"
 #include "rsc_kernels.h"
@@ -168,6 +170,34 @@ struct rsc_context {
     // [0] speculation inputs built, [1] kernels enqueued, [2] counts back (sync), [3] return
     double host_us[4] = {0, 0, 0, 0};
     bool direct_counts = true;  // env RSC_DIRECT_COUNTS=0 restores the HBM buffer + D2H copy
+    // PnP scan: a hypothesis that cannot reach mRansacMinInliers after the first half of the thread's
+    // point slices is not counted further (rsc_scanbound.h); env RSC_SCAN_BOUND=0/1,
+    // rsc_context_set_scan_bound.  Off: every stored count is exact.
+    bool scan_bound = true;
+    // The last PnP round's scan launch, kept so that the parity hook (rsc_pnp_last_hypotheses) can
+    // count that round again with the bound off: `pending` is set by a round that ran with the bound
+    // on and cleared by the recount and, first thing, by the context's next speculation of any kind.
+    // The tables, the betas results and the outputs the launch names stay valid until that next
+    // speculation; the blob path's records do not (a Refine reuses the descriptor buffer), so their
+    // bytes are kept.  The problem table names every solver's point buffers, which live only as long
+    // as the solver: the round notes how many of the context's PnP solvers had been destroyed
+    // (`pnp_destroyed`, which ~rsc_pnp counts up), and once that number has moved the hook reports an
+    // error for that round (`lost`) instead of launching over freed memory.
+    struct PnpScanLaunch {
+        bool pending = false, use_args = false;
+        bool lost = false;        // a PnP solver of the context was destroyed before a recount
+        uint64_t destroyed = 0;   // *pnp_destroyed when the round was launched
+        int ppt = 0, nwg = 0, mask_words = 0, total = 0;
+        int32_t* counts = nullptr;      // where the round's counts went (pinned memory or HBM)
+        int32_t* counts_dev = nullptr;  // the fused round's HBM copy, or null
+        RoundArgs args;                 // argument path: the round's records
+        std::vector<DevPnP> probs;      // blob path: the problem table and the records
+        std::vector<LaunchProb> lps;
+        void forget() { pending = lost = false; }  // a new round: nothing left to recount
+    } pnp_scan_last;
+    // PnP solvers of this context destroyed so far.  Shared with the solvers, which may outlive the
+    // context (a binding's objects are collected in any order), so a solver never follows `ctx` to it.
+    std::shared_ptr<std::atomic<uint64_t>> pnp_destroyed = std::make_shared<std::atomic<uint64_t>>(0);
     bool fused_refine = true;   // env RSC_FUSED_REFINE=0: the replay's Refine always as its own launch
     bool dma_upload = false;    // env RSC_DMA_UPLOAD=1: descriptors by hipMemcpyAsync instead of the copy kernel
     // eigen stage in the rows form when it has <= W workgroups (small, latency-bound launches such as
@@ -219,7 +249,10 @@ struct rsc_pnp {
     rsc_stream* stream = nullptr;  // shared rand() stream (rsc_pnp_bind_stream) or null: own stream
     RngStream own_rng;             // the own stream, parked while bound (st.rng follows the shared one)
     std::vector<float> h_p2d, h_p3d;  // host copies (the gated events' PoseOptimization problems)
+    std::shared_ptr<std::atomic<uint64_t>> ctx_destroyed;  // the context's pnp_destroyed
     ~rsc_pnp() {
+        // the context's last round may name the buffers freed below: it cannot be counted again
+        if (ctx_destroyed) ctx_destroyed->fetch_add(1, std::memory_order_relaxed);
         for (void* p : {(void*)d_pts, (void*)d_uv, (void*)d_pws, (void*)d_us, (void*)d_als, (void*)d_best,
                         (void*)d_refined})
             if (p) (void)hipFree(p);

@@ -176,9 +176,11 @@ hipError_t launch_pnp_solve_split(int ns, int nwgE, const int2* wgtE, int nwgB, 
 // launch problem lp reaches its min_inliers.
 // bs: the betas stage's results; the scan keeps each hypothesis' approximation with the smallest error
 // (a scan workgroup's chunk holds at most 64 hypotheses) and writes its pose to poses[record].
+// bound: a hypothesis that cannot reach min_inliers after the first half of the thread's slices is not
+// counted further, and its stored count is the count so far (rsc_scanbound.h); false: every count is exact.
 hipError_t launch_pnp_scan(int ppt, int nwg, const DevPnP* probs, const LaunchProb* lps, const RoundArgs* args,
                            const int4* wgt, const BetasScratch& bs, float* poses, int32_t* counts, int32_t* counts_dev, uint64_t* masks,
-                           int mask_words, int32_t* qual, hipStream_t st);
+                           int mask_words, int32_t* qual, bool bound, hipStream_t st);
 // Workgroups of pnp_scan_kernel<ppt> one CU holds at once (the runtime's occupancy query for the
 // instantiated kernel: registers and LDS as built).
 hipError_t pnp_scan_occupancy(int ppt, int* wgs_per_cu);

@@ -31,7 +31,7 @@ EXPORTED = [
     "rsc_version", "rsc_status_string", "rsc_context_create", "rsc_context_destroy", "rsc_context_set_stream",
     "rsc_context_synchronize", "rsc_context_last_timing", "rsc_context_last_kernel_timing", "rsc_diag_host_timing", "rsc_context_enable_timing", "rsc_selftest_math",
     "rsc_context_set_eig_rows", "rsc_context_set_eig_split", "rsc_context_set_sim3opt_helpers",
-    "rsc_context_set_round_args", "rsc_diag_round_paths",
+    "rsc_context_set_round_args", "rsc_context_set_scan_bound", "rsc_pnp_last_counts_raw", "rsc_diag_round_paths",
     "rsc_pnp_create", "rsc_pnp_destroy", "rsc_pnp_set_ransac_parameters", "rsc_pnp_iterate", "rsc_pnp_find",
     "rsc_pnp_last_inliers",
     "rsc_pnp_iterate_many", "rsc_pnp_reset", "rsc_pnp_get_state", "rsc_pnp_last_samples", "rsc_pnp_last_hypotheses",
@@ -1114,6 +1114,7 @@ def load_library(path: str = LIB_PATH):
     L.rsc_context_enable_timing.argtypes = [vp, C.c_int]
     L.rsc_context_set_eig_rows.argtypes = [vp, C.c_int]
     L.rsc_context_set_round_args.argtypes = [vp, C.c_int]
+    L.rsc_context_set_scan_bound.argtypes = [vp, C.c_int]
     L.rsc_diag_round_paths.argtypes = [vp, C.POINTER(C.c_int64)]
     L.rsc_diag_fill_staging.argtypes = [vp, C.c_int]
     L.rsc_diag_fill_staging.restype = C.c_int64
@@ -1134,6 +1135,7 @@ def load_library(path: str = LIB_PATH):
     L.rsc_pnp_get_state.argtypes = [vp, i32p]
     L.rsc_pnp_last_samples.argtypes = [vp, i32p, C.c_int]
     L.rsc_pnp_last_hypotheses.argtypes = [vp, i32p, f32p, C.c_int]
+    L.rsc_pnp_last_counts_raw.argtypes = [vp, i32p, C.c_int]
     L.rsc_sim3_last_hypotheses.argtypes = [vp, i32p, f32p, C.c_int]
     L.rsc_mlpnp_last_counts.argtypes = [vp, i32p, C.c_int]
     L.rsc_sim3_create.argtypes = [vp, C.POINTER(Sim3Input), C.c_uint32, C.POINTER(vp)]
@@ -1336,6 +1338,11 @@ class Context:
         device (default on); off: every round uploads its descriptor blob."""
         _check(load_library().rsc_context_set_round_args(self.h, int(bool(on))), "set_round_args")
 
+    def set_scan_bound(self, on: bool):
+        """PnP scan: stop counting a hypothesis that cannot reach mRansacMinInliers after the first half
+        of the point slices (default on); off: every hypothesis is counted in full."""
+        _check(load_library().rsc_context_set_scan_bound(self.h, int(bool(on))), "set_scan_bound")
+
     def round_paths(self):
         """Diagnostic counters of the context's PnP rounds: on the argument path, on the blob path,
         and uploads of the resident problem table."""
@@ -1526,6 +1533,15 @@ class PnPSolver:
         if n < 0:
             _check(n, "last_hypotheses")
         return cnt[:n], pos[:n]
+
+    def last_counts_raw(self, cap: int = 4096) -> np.ndarray:
+        """The last launch's counts as the round left them: a hypothesis the scan bound cut short shows
+        its count over the first segment (before last_hypotheses() has recounted the round)."""
+        cnt = np.zeros(cap, np.int32)
+        n = load_library().rsc_pnp_last_counts_raw(self.h, cnt, cap)
+        if n < 0:
+            _check(n, "last_counts_raw")
+        return cnt[:n]
 
 
 def pnp_iterate_many(solvers, n_iterations, with_masks: bool = True):
